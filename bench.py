@@ -23,6 +23,13 @@ job's pixels over the slowest rank's time ("scaling": "strong"), the per-rank ti
 `--stub` replaces the GPU batch by a CPU stand-in (gloo instead of RCCL): the rank / shard /
 reduce logic of this file runs unchanged, which is what tests/test_bench_ranks.py drives at
 world size 2.
+
+A plain run does only what the headline needs: the inputs (synthesised, and checked against the
+oracle, in worker processes), upload, the parity decode, `--warmup` untimed and `--steps` timed
+decodes, the line.  `--full` adds everything else the line used to carry: the roofline (per-stage
+hipEvent decodes), the CPU baselines, the T2 upload figure, the one-stream form and the BASELINE
+config 1 / 2 / 5 extras.  `--dump-outputs DIR` writes what the last timed decode left in HBM
+(every DIB checksum, a seeded sample of DIB bytes) as float .npy files after the timed steps.
 """
 import argparse
 import json
@@ -48,8 +55,10 @@ def parse_args(argv=None):
     ap.add_argument("--distinct", type=int, default=64, help="distinct synthetic pictures per GPU (replicated to --images)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (rank 0, N=1 only)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the BASELINE config 2 / config 5 / staging-pipeline extras (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, CPU baselines, T2 upload figure, one-stream form and extras (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the cpu_baseline leg (rank 0, N=1 only)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the BASELINE config 2 / config 5 / staging-pipeline extras (rank 0, N=1)")
     ap.add_argument("--no-split", action="store_true", help="decode the batch on ONE stream (profiling runs: keeps the per-kernel averages those of whole-batch launches); "
                     "default: the library's own choice, two halves on two streams for a batch this size")
     ap.add_argument("--strong", action="store_true", help="strong scaling: one job of --job-images mixed-size files, LPT-partitioned over the ranks")
@@ -170,19 +179,96 @@ def cpu_model():
     return "unknown"
 
 
+def usable_cores():
+    """Cores this process may use: its affinity, capped by the cgroup CPU quota (a container's quota, not the visible core count)."""
+    ncore = len(os.sched_getaffinity(0))
+    try:
+        q, per = open("/sys/fs/cgroup/cpu.max").read().split()
+        if q != "max":
+            ncore = max(1, min(ncore, int(q) // int(per)))
+    except (OSError, ValueError):
+        pass
+    return ncore
+
+
+INPUT_WORKERS_MAX = 16      # the input pool of a plain run: never more processes than this, whatever the box shows
+
+
+def input_pool(world):
+    """Worker processes (spawned: no GPU state crosses) that synthesise the inputs and decode them with the oracle, this rank's share of the cores."""
+    import concurrent.futures as cf
+    import multiprocessing as mp
+    n = max(1, min(INPUT_WORKERS_MAX, usable_cores()) // world)
+    return cf.ProcessPoolExecutor(max_workers=n, mp_context=mp.get_context("spawn"))
+
+
+def _synth_worker(spec):
+    """One synthetic picture of the workload: spec = (width, height, seed) -> the file's bytes (deterministic in spec)."""
+    from oracle import harness as H
+    w, h, seed = spec
+    return H.synth_jpeg(width=w, height=h, hs=2, vs=2, quality=85, seed=seed)
+
+
+_GATE_ORC = None
+
+
+def _oracle_worker(data):
+    """The oracle's DIB checksum of one file (the parity gate's reference value), one oracle instance per worker process."""
+    global _GATE_ORC
+    from oracle import harness as H
+    import jpegsnoop_amd as J
+    if _GATE_ORC is None:
+        _GATE_ORC = H.oracle_backend()
+    H.drive(_GATE_ORC, data)
+    return J.dib_checksum_numpy(_GATE_ORC.dib())
+
+
+def cpu_single_core(H, orc, files, budget):
+    """cpu_baseline (--full): the oracle on this workload's distinct pictures, one thread, until `budget` seconds are spent."""
+    n, spent = 0, 0.0
+    for f in files:
+        if spent > budget:
+            break
+        t1 = time.perf_counter()
+        H.drive(orc, f)
+        spent += time.perf_counter() - t1
+        n += 1
+    return n, spent
+
+
+DUMP_IMAGES = 16            # --dump-outputs: DIBs sampled (over all ranks)
+DUMP_SAMPLES = 1 << 18      # ... bytes sampled per DIB: 16 x 256 Ki float32 = 16 MB
+
+
+def dump_outputs(path, batch, sums, rank, world, stub):
+    """--dump-outputs: what the last timed decode left in HBM.  dib_checksums.npy: every image's 64-bit DIB checksum as four 16-bit words
+    (float64, exact); dib_sample.npy: DUMP_SAMPLES bytes of each of DUMP_IMAGES DIBs at seeded positions (float32, 0..255);
+    dib_sample_images.npy: which images.  Rank r > 0 of a multi-rank run adds _rank<r> to the names."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    sums = np.asarray(sums, dtype=np.uint64)
+    words = np.stack([(sums >> np.uint64(s)) & np.uint64(0xFFFF) for s in (48, 32, 16, 0)], axis=1).astype(np.float64)
+    np.save(os.path.join(path, "dib_checksums%s.npy" % sfx), words)
+    if stub or not len(batch):
+        return
+    rng = np.random.default_rng(20240 + rank)
+    idx = np.sort(rng.choice(len(batch), min(len(batch), max(1, DUMP_IMAGES // world)), replace=False))
+    rows = []
+    for i in idx:
+        d = batch.dib(int(i)).reshape(-1)
+        rows.append(d[rng.integers(0, d.size, DUMP_SAMPLES)].astype(np.float32))
+    np.save(os.path.join(path, "dib_sample%s.npy" % sfx), np.stack(rows))
+    np.save(os.path.join(path, "dib_sample_images%s.npy" % sfx), idx.astype(np.float64))
+
+
 def cpu_all_cores(args, rank):
     """The same CPU path on every host core: independent decoder instances, one per process (the reference is single-threaded,
     DoBatchFileProcess run N-wide is N instances) -- bounded to a few seconds."""
     try:
         import concurrent.futures as cf
         import multiprocessing as mp
-        ncore = len(os.sched_getaffinity(0))
-        try:                                                               # a container's CPU quota, not the visible core count, is what it can use
-            q, per = open("/sys/fs/cgroup/cpu.max").read().split()
-            if q != "max":
-                ncore = max(1, min(ncore, int(q) // int(per)))
-        except (OSError, ValueError):
-            pass
+        ncore = usable_cores()
         if ncore <= 1:
             return None
         reps = 16
@@ -463,15 +549,15 @@ def main():
         sys.exit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s)")
 
     import numpy as np
-    import torch
-    import torch.distributed as dist
     import jpegsnoop_amd as J
 
     stub = args.stub
     dev = None
+    pool = synth_jobs = None
+    t_gen0 = time.time()
     if not stub:
         import __graft_entry__ as G
-        from oracle import harness as H            # checker + input generator only (cpu_baseline leg, parity gate)
+        from oracle import harness as H            # checker + input generator only (parity gate, cpu_baseline leg)
         if not (os.path.exists(J.LIB_PATH) and os.path.exists(H.ORC_SO) and os.path.exists(H.SYNTH_SO)):
             if local_rank == 0:
                 G.build()
@@ -481,6 +567,19 @@ def main():
                         break
                     time.sleep(0.5)
                 time.sleep(1.0)
+        # the inputs are synthesised in worker processes while this one brings up torch and the device
+        if args.strong:
+            synth_keys = sorted(set(job_plan(args.job_images, args.distinct)))
+            specs = [JOB_KINDS[k] + (job_seed(k, sd),) for k, sd in synth_keys]
+        else:
+            synth_keys = list(range(args.distinct))
+            specs = [(args.width, args.height, 1000 * rank + i + 1) for i in synth_keys]
+        pool = input_pool(world)
+        synth_jobs = [pool.submit(_synth_worker, s) for s in specs]
+
+    import torch
+    import torch.distributed as dist
+    if not stub:
         dev_index = 0 if args.share_device else local_rank
         if torch.cuda.device_count() <= dev_index:
             sys.exit(f"bench.py: rank {rank} needs GPU {dev_index}, {torch.cuda.device_count()} visible")
@@ -509,15 +608,12 @@ def main():
     shard_info = None
     if args.strong:
         plan = job_plan(args.job_images, args.distinct)
-        distinct_keys = sorted(set(plan))
         if stub:
             costs = [stub_cost(k, sd) for k, sd in plan]
         else:
-            t0 = time.time()
-            for k, sd in distinct_keys:                                   # deterministic: every rank makes the same files, and so the same costs
-                w, h = JOB_KINDS[k]
-                job_files[(k, sd)] = H.synth_jpeg(width=w, height=h, hs=2, vs=2, quality=85, seed=job_seed(k, sd))
-            t_gen = time.time() - t0
+            for key, fut in zip(synth_keys, synth_jobs):              # deterministic: every rank makes the same files, and so the same costs
+                job_files[key] = fut.result()
+            t_gen = time.time() - t_gen0
             costs = [len(job_files[e]) for e in plan]
         bins = J.partition_lpt(costs, world)
         gidx = bins[rank]
@@ -538,58 +634,57 @@ def main():
             for k in keys:
                 batch.add_jpeg(job_files[k])                 # every image has its own bytes in the raw arena
         else:
-            t0 = time.time()
-            files = [H.synth_jpeg(width=args.width, height=args.height, hs=2, vs=2, quality=85, seed=1000 * rank + i + 1)
-                     for i in range(args.distinct)]
-            t_gen = time.time() - t0
+            files = [fut.result() for fut in synth_jobs]
+            t_gen = time.time() - t_gen0
             for f in files:
                 batch.add_jpeg(f)
             batch.tile(args.images)                          # physical replication: every image has its own bytes in the raw arena
+        # the oracle's checksum of every distinct picture of this shard, in the workers while this process uploads and decodes
+        gate_keys = sorted(set(keys))
+        gate_jobs = [pool.submit(_oracle_worker, job_files[k] if args.strong else files[k]) for k in gate_keys]
         t0 = time.perf_counter()
         batch.upload()                                   # pinned host -> HBM, outside the timed region
         t_upload_first = time.perf_counter() - t0        # includes the one-time hipMalloc of the arenas
-        lib.jsnoop_batch_set_options(batch._h, 1, 0, 0)  # marks the batch dirty: the next upload() repeats only the H2D copies
-        t0 = time.perf_counter()
-        batch.upload()                                   # returns after the copy stream has drained
-        t_upload = time.perf_counter() - t0
+        if args.full:
+            lib.jsnoop_batch_set_options(batch._h, 1, 0, 0)  # marks the batch dirty: the next upload() repeats only the H2D copies
+            t0 = time.perf_counter()
+            batch.upload()                                   # returns after the copy stream has drained
+            t_upload = time.perf_counter() - t0
     pixels = batch.pixels()
     alg_bytes = batch.algorithmic_bytes()
 
     # The decode form is the library's default (jsnoop_batch_set_split(0): two halves of a batch this size on two streams) unless --no-split.
     if not stub:
         batch.set_split(1 if args.no_split else 0)
-    # ---- parity gate + cpu_baseline sample (the oracle is only the checker / the baseline here) ----
+    # ---- parity gate (the oracle is only the checker here) + (--full) cpu_baseline ----
     batch.decode(); batch.sync()
     sums = batch.dib_checksums()
     flags = [batch.info(i)["flags"] for i in range(len(batch))]
     paths = [batch.info(i)["path"] for i in range(len(batch))]
     n_cpu, cpu_time, errors = 0, 0.0, 0
-    budget = args.cpu_seconds if (rank == 0 and world == 1 and not stub and not args.strong) else 0.0
+    budget = args.cpu_seconds if (args.full and rank == 0 and world == 1 and not stub and not args.strong) else 0.0
     all_cores = ref_info = cfg1 = None
     orc = None
     n_checked = 0
     if not stub:
-        # EVERY rank checks EVERY distinct picture of its shard against the oracle (ranks work side by side; 64 x 1080p = ~9 s):
-        # no image is reported bit-exact on the strength of its flags alone.  The cpu_baseline figure is the time of the first
-        # `budget` seconds of these same oracle decodes (rank 0, N = 1).
-        orc = H.oracle_backend()
+        # EVERY rank checks EVERY distinct picture of its shard against the oracle (in the input workers, started before the upload):
+        # no image is reported bit-exact on the strength of its flags alone.
         members = {}
         for i, k in enumerate(keys):
             members.setdefault(k, []).append(i)
-        for k in sorted(members):
-            t1 = time.perf_counter()
-            H.drive(orc, job_files[k] if args.strong else files[k])
-            dt = time.perf_counter() - t1
-            want = J.dib_checksum_numpy(orc.dib())
+        for k, fut in zip(gate_keys, gate_jobs):
+            want = fut.result()
             for i in members[k]:
                 errors += int(int(sums[i]) != want)
                 n_checked += 1
-            if budget > 0 and cpu_time <= budget:
-                n_cpu += 1
-                cpu_time += dt
+        pool.shutdown()
         assert n_checked == len(batch), "parity gate: every image of the shard must have been compared"
+        if args.full:
+            orc = H.oracle_backend()
     errors += sum(1 for f in flags if f)
     if budget > 0:
+        # the oracle on this workload's pictures, one thread, for `budget` seconds
+        n_cpu, cpu_time = cpu_single_core(H, orc, files, budget)
         all_cores = cpu_all_cores(args, rank)
         if H.have_ref():                  # the compiled reference, when its .so travelled (never reads /root/reference)
             ref = H.ref_backend()
@@ -631,14 +726,17 @@ def main():
     errors += sum(1 for f in flags2 if f)
     sums2 = batch.dib_checksums()
     errors += int((sums2 != sums).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch, sums2, rank, world, stub)
 
-    # per-stage device time (hipEvents on the batch stream, same resident batch) -- taken in the ONE-stream form whatever form was timed above:
-    # in a split decode every kernel shares the chip with a kernel of the other half, its launch duration describes the sharing, not the kernel
     decode_form = "stub" if stub else ("two halves on two streams (library default)" if batch.split_parts() == 2 else "one stream")
-    if not stub:
-        batch.set_split(1)
-    ms_whole, stages = batch.decode_timed(max(3, min(10, args.steps)))
-    dom = max(stages, key=stages.get)
+    if args.full:
+        # per-stage device time (hipEvents on the batch stream, same resident batch) -- taken in the ONE-stream form whatever form was timed above:
+        # in a split decode every kernel shares the chip with a kernel of the other half, its launch duration describes the sharing, not the kernel
+        if not stub:
+            batch.set_split(1)
+        ms_whole, stages = batch.decode_timed(max(3, min(10, args.steps)))
+        dom = max(stages, key=stages.get)
 
     my_ck = shard_checksum(sums, gidx)
     tot_px, max_el, job_ck, tot_err = J.reduce_job_stats(pixels * args.steps, elapsed, my_ck, errors, rdev)
@@ -671,7 +769,7 @@ def main():
                   "ms_spread": round((max(per_rank_ms) - min(per_rank_ms)) / max(per_rank_ms), 4) if max(per_rank_ms) > 0 else 0.0}
 
     extra = {}
-    if rank == 0 and world == 1 and not stub and not args.strong and not args.no_split:
+    if args.full and rank == 0 and world == 1 and not stub and not args.strong and not args.no_split:
         # the same resident batch in the one-stream form, beside the headline (which ran the library's default form)
         try:
             batch.set_split(1)
@@ -688,7 +786,7 @@ def main():
             extra["one_stream"] = {"error": repr(e)}
     if not stub:
         batch.set_split(0)
-    if rank == 0 and world == 1 and not stub and not args.no_extras and not args.strong:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_extras and not args.strong:
         try:
             extra.update(extras_single_gpu(J, H, orc, np))
         except Exception as e:                                       # beside the headline, never a reason to lose it
@@ -714,14 +812,15 @@ def main():
                        "decode_form": decode_form},
             "bit_exact": tot_err == 0, "parity_errors": tot_err,
             "per_rank_ms_per_step": per_rank_ms, "job_checksum": "%016x" % job_ck, "images_oracle_checked_per_rank": n_checked,
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(alg_bytes / (stages[dom] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": round(alg_bytes / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(stages[dom], 4),
-                         "pipeline": {"ms": round(ms_whole, 4), "achieved": round(alg_bytes / (ms_whole * 1e-3) / 1e9, 1),
-                                      "frac": round(alg_bytes / (ms_whole * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
-                         "stages_ms": {k: round(v, 4) for k, v in stages.items()},
-                         "measured_in": "one-stream decodes of the same resident batch (hipEvents between the stages)"},
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(alg_bytes / (stages[dom] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS,
+                               "unit": "GB/s", "frac": round(alg_bytes / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
+                               "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(stages[dom], 4),
+                               "pipeline": {"ms": round(ms_whole, 4), "achieved": round(alg_bytes / (ms_whole * 1e-3) / 1e9, 1),
+                                            "frac": round(alg_bytes / (ms_whole * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
+                               "stages_ms": {k: round(v, 4) for k, v in stages.items()},
+                               "measured_in": "one-stream decodes of the same resident batch (hipEvents between the stages)"}
         if budget > 0 and n_cpu:
             out["cpu_baseline"] = {"value": round(n_cpu * args.width * args.height / cpu_time / 1e6, 2), "unit": "Mpixels/s", "cores": 1, "cpu_model": cpu_model(),
                                    "kind": "port", "sample": f"{n_cpu} x {args.width}x{args.height} 4:2:0 images of this workload, oracle/oracle_imgdecode.c, "
@@ -735,7 +834,7 @@ def main():
                 out["cpu_baseline"]["all_cores"] = all_cores
         # measured HBM traffic of the dominant kernel (rocprofv3 PMC passes of this same workload, tools/pmc_collect.sh)
         tf = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tf) and not stub:
+        if args.full and os.path.exists(tf) and not stub:
             try:
                 tj = json.load(open(tf))
                 if tj.get("kernel") == dom and tj.get("images_per_launch"):
@@ -748,6 +847,7 @@ def main():
         if not stub and not args.strong:
             comp = int(sum(len(f) for f in files) * (args.images / args.distinct))
             out["setup_s"] = {"synth": round(t_gen, 1), "first_upload_with_alloc": round(t_upload_first, 3)}
+        if args.full and not stub and not args.strong:
             out["pcie_inclusive_T2"] = {"h2d_ms": round(t_upload * 1e3, 3), "compressed_bytes": comp, "h2d_GBps": round(comp / t_upload / 1e9, 1),
                                         "mpix_per_s_serial": round(pixels / (t_upload + max_el / args.steps) / 1e6, 1),
                                         "note": "timing scope T2, serial form: pinned H2D of the whole compressed batch (stream drained), then decode; "

@@ -84,10 +84,40 @@ def test_strong_scaling_job_is_partitioned_by_bytes_and_its_union_is_the_job():
 
 
 def test_single_rank_stub_line_has_the_contract_keys():
-    out = last_json(run_bench("--stub", "--images", "4", "--distinct", "2", "--steps", "2", "--warmup", "1", "--width", "64", "--height", "48"))
+    out = last_json(run_bench("--stub", "--full", "--images", "4", "--distinct", "2", "--steps", "2", "--warmup", "1", "--width", "64", "--height", "48"))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out
     assert out["n_gpus"] == 1 and out["roofline"]["bound"] == "hbm" and "workload" in out["config"]
+
+
+def test_plain_stub_line_has_the_headline_keys_and_no_full_extras():
+    """Without --full the line carries the headline alone: the same keys and meaning, none of the figures that take runs of their own."""
+    steps = 4
+    out = last_json(run_bench("--stub", "--images", "4", "--distinct", "2", "--steps", str(steps), "--warmup", "1", "--width", "64", "--height", "48"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config", "bit_exact"):
+        assert k in out
+    assert out["steps"] == steps and out["ms_per_step"] >= 2.0 and out["bit_exact"] and out["value"] > 0
+    assert abs(out["value"] - 4 * 64 * 48 / (out["ms_per_step"] * 1e-3) / 1e6) < 0.05 * out["value"] + 0.2
+    for k in ("roofline", "cpu_baseline", "one_stream", "staging_pipeline", "pcie_inclusive_T2"):
+        assert k not in out
+
+
+def test_dump_outputs_are_float_and_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: every image's DIB checksum as four exact 16-bit words (float64); the same arguments give the same arrays."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        last_json(run_bench("--stub", "--images", "6", "--distinct", "2", "--steps", "2", "--warmup", "1", "--width", "64", "--height", "48",
+                            "--dump-outputs", str(d)))
+        w = np.load(d / "dib_checksums.npy")
+        assert w.dtype == np.float64 and w.shape == (6, 4) and sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        got.append(w)
+    assert np.array_equal(got[0], got[1])
+    sums = [sum(int(x) << s for x, s in zip(row, (48, 32, 16, 0))) for row in got[0]]
+    assert sums == [int(x) for x in bench.StubBatch([(64, 48)] * 6, range(6), 0.0).dib_checksums()]
 
 
 def test_world_size_mismatch_fails_loudly():

@@ -43,3 +43,29 @@ def test_without_the_switch_the_launcher_refuses_when_devices_are_missing():
     p, out = _run("--gpus", "2", "--strong", "--job-images", "8", "--steps", "1")
     assert p.returncode != 0 and out is None
     assert (b"bench.py: --gpus 2 requested but only %d HIP device(s) are visible" % have) in p.stderr
+
+
+def test_plain_line_and_dumped_outputs_match_the_oracle(tmp_path, harness):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full): K timed steps, the headline keys, bit-exact; the dumped DIB checksums
+    of the last timed step are the oracle's, image by image; the DIB sample is float32 bytes.  With --full the roofline comes back."""
+    import numpy as np
+    import jpegsnoop_amd as J
+    w, h, images, distinct = 320, 240, 8, 3
+    work = ("--images", str(images), "--distinct", str(distinct), "--width", str(w), "--height", str(h), "--warmup", "1")
+    p, out = _run("--steps", "3", "--dump-outputs", str(tmp_path), *work)
+    assert p.returncode == 0 and out, p.stderr.decode()[-1500:]
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["bit_exact"] and out["value"] > 0 and "roofline" not in out
+    words = np.load(tmp_path / "dib_checksums.npy")
+    assert words.dtype == np.float64 and words.shape == (images, 4)
+    sums = [sum(int(x) << s for x, s in zip(row, (48, 32, 16, 0))) for row in words]
+    orc = harness.oracle_backend()
+    want = []
+    for i in range(distinct):
+        harness.drive(orc, harness.synth_jpeg(width=w, height=h, hs=2, vs=2, quality=85, seed=i + 1))
+        want.append(J.dib_checksum_numpy(orc.dib()))
+    orc.close()
+    assert sums == [want[i % distinct] for i in range(images)]
+    sample = np.load(tmp_path / "dib_sample.npy")
+    assert sample.dtype == np.float32 and sample.ndim == 2 and sample.shape[0] == images and sample.min() >= 0 and sample.max() <= 255
+    p, full = _run("--steps", "2", "--full", "--no-extras", "--cpu-seconds", "1", *work)
+    assert p.returncode == 0 and full and full["bit_exact"] and full["roofline"]["bound"] == "hbm", p.stderr.decode()[-1500:]

@@ -8,7 +8,7 @@ cp jpegsnoop_amd/libjsnoop_gpu.so /tmp/libjsnoop_gpu.orig.so
 for E in "$@"; do
   IFS='|' read -r LABEL SO ENVS ARGS <<< "$E"
   [ "$SO" != "-" ] && cp $SO jpegsnoop_amd/libjsnoop_gpu.so
-  env $ENVS python bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras $ARGS 2>$OUT/$LABEL.err | tail -1 > $OUT/bench_$LABEL.json
+  env $ENVS python bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras $ARGS 2>$OUT/$LABEL.err | tail -1 > $OUT/bench_$LABEL.json
   cp /tmp/libjsnoop_gpu.orig.so jpegsnoop_amd/libjsnoop_gpu.so
 done
 python - <<PY

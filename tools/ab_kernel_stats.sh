@@ -3,9 +3,10 @@
 # every variant build, same box, same call; results in gpurun_out/<tag>/<name>_kernel_stats.csv (+ the bench line of each run)
 TAG=$1; shift
 OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
+ROOT=$PWD
 export TMPDIR=/tmp
 run() {   # name
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$1 -o p -- python $GRAFT_REPO_ROOT/bench.py --steps ${AB_STEPS:-10} --warmup 2 --cpu-seconds 0 --no-extras --no-split > $OUT/bench_$1.json 2>$OUT/$1.err)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$1 -o p -- python $ROOT/bench.py --full --steps ${AB_STEPS:-10} --warmup 2 --cpu-seconds 0 --no-extras --no-split > $OUT/bench_$1.json 2>$OUT/$1.err)
   F=$(find $OUT/prof_$1 -name '*kernel_stats.csv' | head -1)
   [ -n "$F" ] && cp $F $OUT/$1_kernel_stats.csv
   rm -rf $OUT/prof_$1

@@ -2,13 +2,14 @@
 those registers are in flight.  This check compiles the kernels to assembly and, for every k_idct_color instance, lists every instruction that READS a
 register a `global_load_*` of the MCU loop writes: only the masking `v_and_b32` (rows), the `v_add_u32` of the DC word and the loads themselves may appear;
 a `v_mov` / copy of such a register would read it before its data has landed.   usage: python tools/check_inflight_regs.py   (CPU only, ~1 min)"""
-import os, re, subprocess, sys, tempfile
+import os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "jpegsnoop_amd", "csrc", "jsnoop_kernels.hip")
-out = os.path.join(tempfile.gettempdir(), "jsnoop_kernels_check.s")
+out = os.path.join(tempfile.mkdtemp(prefix="jsnoop_regs_"), "jsnoop_kernels_check.s")     # a private directory: no clash with another user's run
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--cuda-device-only", "-S",
                        "-I" + os.path.dirname(src), "-o", out, src], stderr=subprocess.DEVNULL)
 text = open(out).read()
+shutil.rmtree(os.path.dirname(out), ignore_errors=True)
 bad = 0
 for m in re.finditer(r"^(_Z12k_idct_colorILi([1-4])E\w+):\s*; @.*?^\.Lfunc_end", text, re.S | re.M):     # (<0>, the any-layout kernel, leaves loads and waits to the compiler)
     body = m.group(0).split("\n")

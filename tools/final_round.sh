@@ -5,7 +5,7 @@ TAG=${1:-rXX_final}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 bash tools/profile_round.sh $TAG > $OUT/profile_round.log 2>&1
-python bench.py 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
+python bench.py --full 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
 timeout 400 python tools/fuzz_1080p_timing.py 1000 17 > $OUT/fuzz_1080p_timing.log 2>&1; cp gpurun_out/fuzz_1080p_timing.json $OUT/ 2>/dev/null
 python tools/small_jobs.py 1 2 4 8 16 32 48 64 96 128 256 2>/dev/null | tail -1 > $OUT/small_jobs.json
 python tools/call_latency.py 2>/dev/null | tail -1 > $OUT/call_latency.json

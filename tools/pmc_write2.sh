@@ -5,7 +5,7 @@
 TAG=$1; shift
 ROOT=$GRAFT_REPO_ROOT; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--images 256 --distinct 16 --steps 2 --warmup 1 --cpu-seconds 0 --no-extras --no-split"
+ARGS="--full --images 256 --distinct 16 --steps 2 --warmup 1 --cpu-seconds 0 --no-extras --no-split"
 run_lib() {
   local NAME=$1 i=0
   mkdir -p $OUT/$NAME

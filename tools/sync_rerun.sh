@@ -1,9 +1,10 @@
 #!/bin/bash
 # (experiment 16 of profiles/r06_experiments.txt) the first k_sync launch three times in a row (variant r06_sync3x): what a warm cache is worth to the walks
 OUT=$PWD/gpurun_out/sync3x; mkdir -p $OUT; export TMPDIR=/tmp
+ROOT=$PWD
 cp jpegsnoop_amd/libjsnoop_gpu.so /tmp/orig.so; cp gpurun_variants/lib_r06_sync3x.so jpegsnoop_amd/libjsnoop_gpu.so
 for N in 32 64 256 1024; do
-  (cd /tmp && JSNOOP_CAND=0 JSNOOP_SUB_WL=7 rocprofv3 --kernel-trace --output-format csv -d $OUT/p$N -o p -- python $GRAFT_REPO_ROOT/bench.py --images $N --distinct 16 --steps 3 --warmup 1 --cpu-seconds 0 --no-extras --no-split > $OUT/b$N.log 2>&1)
+  (cd /tmp && JSNOOP_CAND=0 JSNOOP_SUB_WL=7 rocprofv3 --kernel-trace --output-format csv -d $OUT/p$N -o p -- python $ROOT/bench.py --full --images $N --distinct 16 --steps 3 --warmup 1 --cpu-seconds 0 --no-extras --no-split > $OUT/b$N.log 2>&1)
   F=$(find $OUT/p$N -name '*kernel_trace.csv' | head -1)
   python - "$F" $N <<'PY'
 import csv, sys

@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage (GPU box): tools/trace_step.sh <tag> [bench args]  -- kernel trace of the one-stream bench; prints the launches of the LAST decode with their durations
 TAG=$1; shift; OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT/p -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-extras --no-split "$@" > $OUT/bench.log 2>&1)
+ROOT=$PWD
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT/p -o p -- python $ROOT/bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-extras --no-split "$@" > $OUT/bench.log 2>&1)
 F=$(find $OUT/p -name '*kernel_trace.csv' | head -1)
 python - "$F" <<'PY' | tee $OUT/last_decode.txt
 import csv, sys
