@@ -3,6 +3,7 @@
 Python glue shared by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg:
 
 * ``synth_jpeg``      deterministic synthetic JPEG bytes (oracle/libjsnoop_synth.so)
+* ``encode_rgb``      the same encoder on caller-chosen pixels
 * ``parse_jpeg``      a tiny marker walk that extracts exactly what the reference's
                       CjfifDecode hands to CimgDecode (reference source/JfifDecode.cpp:3401-3612
                       DHT, :4576-4650 DQT, :4802-5026 SOF, :5105-5182 SOS, :5310-5324 DRI)
@@ -71,6 +72,8 @@ def _synth_lib():
         _synth.jsynth_encode.restype = C.c_size_t
         _synth.jsynth_encode.argtypes = [C.POINTER(_SynthParams), C.c_void_p, C.c_size_t]
         _synth.jsynth_image_rgb.argtypes = [C.POINTER(_SynthParams), C.c_void_p]
+        _synth.jsynth_encode_rgb.restype = C.c_size_t
+        _synth.jsynth_encode_rgb.argtypes = [C.POINTER(_SynthParams), C.c_void_p, C.c_void_p, C.c_size_t]
     return _synth
 
 
@@ -84,6 +87,22 @@ def synth_jpeg(width=640, height=480, hs=2, vs=2, quality=85, restart_interval=0
     if n > cap:
         buf = np.empty(n, np.uint8)
         n = _synth_lib().jsynth_encode(C.byref(p), buf.ctypes.data, n)
+    return buf[:n].tobytes()
+
+
+def encode_rgb(rgb, hs=2, vs=2, quality=85, restart_interval=0, gray=0, optimize_huffman=0) -> bytes:
+    """Baseline JPEG of caller-chosen pixels: rgb is a (height, width, 3) uint8 array.  A flat 8x8 block keeps only its DC
+    coefficient, so every sample of it decodes to the same value (how tests get exact ties under lossy coding)."""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 3, a.shape
+    h, w = a.shape[:2]
+    p = _SynthParams(w, h, hs, vs, quality, restart_interval, gray, optimize_huffman, 0, 0, 0)
+    cap = w * h * 3 + 65536
+    buf = np.empty(cap, np.uint8)
+    n = _synth_lib().jsynth_encode_rgb(C.byref(p), a.ctypes.data, buf.ctypes.data, cap)
+    if n > cap:
+        buf = np.empty(n, np.uint8)
+        n = _synth_lib().jsynth_encode_rgb(C.byref(p), a.ctypes.data, buf.ctypes.data, n)
     return buf[:n].tobytes()
 
 

@@ -9,6 +9,8 @@ import re
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "jpegsnoop_amd", "csrc", "jsnoop_pair_round.h")
 
@@ -99,3 +101,63 @@ def test_no_instruction_of_the_built_back_end_copies_a_register_in_flight():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_inflight_regs.py")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
     assert p.returncode == 0 and out.count("-> ok") == 4, out
+
+
+@pytest.fixture(scope="module")
+def kernels_asm(tmp_path_factory):
+    """The kernels' gfx950 assembly (hipcc cross-compiles without a GPU), compiled once for the checks below."""
+    import shutil
+    if not (os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import check_inflight_regs
+    finally:
+        sys.path.pop(0)
+    out = tmp_path_factory.mktemp("asm") / "jsnoop_kernels.s"
+    check_inflight_regs.compile_asm(str(out))
+    return out
+
+
+def _check(path):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_inflight_regs.py"), str(path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    return p.returncode, p.stdout.decode()
+
+
+def test_every_hand_vmcnt_wait_of_the_back_end_covers_its_load(kernels_asm):
+    """back_end_pairs waits for its row / DC loads with a hand `s_waitcnt vmcnt(2*np)`: behind each load, 2*np younger VMEM operations must have been
+    issued on every path to the wait that reads its register -- round the loop's back edge (the next pairs' loads and the DIB store) and from the loop's
+    entry (which issues its last DC load twice, the second in the store's place).  The DIB store of layouts 2..4 is issued by lanes 0..31 or 0..15 only,
+    behind an s_cbranch_execz: the check must say so."""
+    rc, out = _check(kernels_asm)
+    assert rc == 0, out
+    assert out.count("hand waits vmcnt(6): all covered") == 1 and out.count("hand waits vmcnt(4): all covered") == 3, out
+    for layout, np_ in ((1, 3), (2, 2), (3, 2), (4, 2)):
+        sec = out.split("k_idct_color<%d>: hand waits" % layout)[1].split("k_idct_color<")[0]
+        # every wait, both ways in: the previous iteration's load and the entry's
+        assert sec.count("-> covered") == 2 * (2 * np_) and "SHORT" not in sec, sec
+        assert sec.count("repeats the one at line") == 1, sec
+        if layout > 1:
+            assert "sits behind the s_cbranch_execz" in sec, sec
+
+
+def test_the_wait_check_fails_without_the_dib_store(kernels_asm, tmp_path):
+    """The same assembly with the MCU loop's DIB store deleted from every one-layout kernel: each of their waits has one VMEM operation too few behind
+    its load on the back-edge path, and the check must fail for all four."""
+    lines, out, cur, in_fn, n = kernels_asm.read_text().split("\n"), [], "", False, 0
+    for l in lines:
+        if re.match(r"^_Z12k_idct_colorILi[1-4]E\w+:", l):
+            in_fn = True
+        elif l.startswith(".Lfunc_end"):
+            in_fn = False
+        if re.match(r"^\s*(\.LBB\w+:|; %bb\.\d+:)", l):
+            cur = l
+        if in_fn and "in Loop" in cur and re.match(r"\s+global_store_dwordx4 v\[\d+:\d+\], v\[\d+:\d+\], off$", l):
+            n += 1
+            continue
+        out.append(l)
+    assert n == 4, n                                              # one DIB store per kernel's loop
+    mutated = tmp_path / "no_dib_store.s"
+    mutated.write_text("\n".join(out))
+    rc, text = _check(mutated)
+    assert rc != 0 and text.count("NOT COVERED") == 4 and "SHORT" in text, text
