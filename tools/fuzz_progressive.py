@@ -1,16 +1,24 @@
 """Randomised transitive parity of the progressive path: random size / sampling / quality / restart interval / scan script;
 the progressive file must decode to the pixels of the baseline file carrying the same coefficients (oracle).
-usage: python tools/fuzz_progressive.py [n_cases] [seed]"""
-import os, sys
+usage: python tools/fuzz_progressive.py [n_cases] [seed] [--pg-lanes N]
+--pg-lanes N aims the run at one form of the scan kernels (JsnoopTuning.pg_lanes: 1, 2, 4, 8, 16 or 64; 0 = by batch size) through jsnoop_set_tuning."""
+import argparse, ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from oracle import harness as H
 import jpegsnoop_amd
 H.build(["oracle", "synth"])
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+ap = argparse.ArgumentParser()
+ap.add_argument("n_cases", nargs="?", type=int, default=60); ap.add_argument("seed", nargs="?", type=int, default=1)
+ap.add_argument("--pg-lanes", type=int, default=0, choices=(0, 1, 2, 4, 8, 16, 64))
+args = ap.parse_args()
+n_cases = args.n_cases
+rng = np.random.default_rng(args.seed)
 orc = H.oracle_backend(); gpu = H.Backend(jpegsnoop_amd.load(), "jsnoop_", "hip")
+tune = jpegsnoop_amd.capi.Tuning(); gpu.lib.jsnoop_tuning_defaults(ctypes.byref(tune)); tune.pg_lanes = args.pg_lanes
+if gpu.lib.jsnoop_set_tuning(ctypes.c_void_p(gpu.h), ctypes.byref(tune)) != 0:
+    sys.exit("jsnoop_set_tuning: " + jpegsnoop_amd.last_error())
 bad = 0
 for k in range(n_cases):
     gray = int(rng.integers(6) == 0)
@@ -31,4 +39,4 @@ for k in range(n_cases):
         for pa, pb in zip(orc.planes(), gpu.planes()):
             if pa is not None and not np.array_equal(pa[:Hh, :W], pb[:Hh, :W]): ok = False
     if not ok: bad += 1; print("case", k, kw, "mode", mode, "MISMATCH")
-print("progressive cases", n_cases, "mismatches", bad)
+print("progressive cases", n_cases, "pg_lanes", args.pg_lanes, "mismatches", bad)
