@@ -321,6 +321,11 @@ int          jsnoop_batch_log(JsnoopBatch*, int i, int histo_en, int stat_clip_e
 int          jsnoop_batch_export_tiff(JsnoopBatch*, int i, const char* path, int mode);
 uint64_t     jsnoop_batch_algorithmic_bytes(const JsnoopBatch*);                   /* sum(scan bytes + DIB bytes), SURVEY.md 8(d) */
 uint64_t     jsnoop_batch_pixels(const JsnoopBatch*);                              /* sum(SOF X*Y) */
+/* HBM that jsnoop_batch_upload requests for the images the batch holds now (0 for an empty batch): every arena of the decode, the allocator's
+ * slack included.  Where the library chooses a form by job size (sub-sequence length, candidate synchronisation) the largest candidate is counted:
+ * the figure is never below the request and never falls when an image is added.  Scratch that only a later request allocates (side-output
+ * passes, second attempts at damaged files) is not part of it.  Host arithmetic only.                                                        */
+uint64_t     jsnoop_batch_device_bytes(const JsnoopBatch*);
 
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
@@ -333,6 +338,94 @@ JsnoopPipeline* jsnoop_pipeline_create(int slots);
 void            jsnoop_pipeline_destroy(JsnoopPipeline*);
 JsnoopBatch*    jsnoop_pipeline_slot(JsnoopPipeline*, int i);
 int             jsnoop_pipeline_run(JsnoopPipeline*, int batches, int d2h, double* out_ms6);
+
+/* ---- job: one call decodes a mixed file list over all devices --------------------------------------------------------------------
+ * The reference's batch loop on the whole node: CJPEGsnoopCore::GenBatchFileList (source/JPEGsnoopCore.cpp:454) builds a file list and
+ * DoBatchFileProcess (:765-845) works through it one file at a time, every file with a freshly reset decoder (CjfifDecode::Reset,
+ * source/JfifDecode.cpp:7306-7308) -- files are independent, so the list shards with no exchange between devices.  A job takes files of
+ * any kind the library decodes (baseline and progressive side by side), spreads them over shards -- one host thread with its own
+ * batches per shard, a shard bound to one device; a device may carry several shards -- and decodes each shard in memory-bounded
+ * rounds.  Every file gets a result; a file never fails the job:
+ *   - what jsnoop_batch_add_jpeg / _add_progressive refuses (not a JPEG, SOF3, four components ...) is JSNOOP_JOB_REFUSED with the text
+ *     jsnoop_last_error() held on the worker thread; the reference's loop notes such a file and moves on;
+ *   - a path that cannot be opened is JSNOOP_JOB_UNREADABLE (the reference returns silently there, :794-798).
+ * A file's pixels, flags, path and log are those of the same file alone in a plain JsnoopBatch, whatever the number of shards, rounds
+ * or partition rule.
+ *
+ * Rounds: a shard fills a round until max_images_per_round is reached or jsnoop_batch_device_bytes of the round's two batches (one
+ * baseline, one progressive, decoded on their own streams) would pass max_round_bytes; an image larger than the budget goes alone in a
+ * round, it is never refused for size.  Each shard has two round slots: reading, header walk, pinned copy and H2D of round r + 1
+ * overlap decode and callbacks of round r.  max_round_bytes = 0 takes HALF of the free HBM hipMemGetInfo reports for the device when
+ * jsnoop_job_run starts, divided by the shards on that device and by the two slots.  The half is a choice, not a measurement: it leaves
+ * room for the scratch jsnoop_batch_device_bytes does not count and for other users of the device.
+ *
+ * Threading: jsnoop_job_* calls on one job come from one thread.  on_file is called on the thread that called jsnoop_job_run, one call
+ * at a time; workers hand finished rounds over through a queue, and a batch handed over is not touched by its worker until the callbacks
+ * for its files have returned (the one-thread-per-handle rule above holds for `batch`).  Files of one round arrive in index order;
+ * rounds of different shards arrive as they finish.
+ *
+ * Failure: the first HIP error on any shard cancels the job -- no shard starts another launch, nothing is retried, jsnoop_job_run
+ * returns -1 and jsnoop_last_error() carries the text.  The multi-device path has been exercised with several shards on one device only. */
+typedef struct JsnoopJob JsnoopJob;
+#define JSNOOP_JOB_MAX_SHARDS 16
+#define JSNOOP_JOB_PENDING    (-1)   /* no result (before jsnoop_job_run, or behind a cancelled / failed run) */
+#define JSNOOP_JOB_OK           0
+#define JSNOOP_JOB_REFUSED      1
+#define JSNOOP_JOB_UNREADABLE   2
+typedef struct JsnoopJobOptions {
+    uint32_t struct_size;           /* sizeof(JsnoopJobOptions) of the caller, read like JsnoopTuning's: shorter is accepted, longer is refused */
+    int32_t  decode_ac;             /* as jsnoop_batch_set_options (default 1)                                                          */
+    int32_t  want_planes;           /* keep the int16 planes (default 0)                                                                */
+    int32_t  enable_log;            /* jsnoop_batch_enable_log on every batch: jsnoop_batch_log works from inside the callback (default 0) */
+    int32_t  max_images_per_round;  /* 0 = 1024                                                                                         */
+    uint64_t max_round_bytes;       /* HBM budget of one round of one shard; 0 = automatic (above)                                       */
+    int32_t  partition;             /* 0 = longest-processing-time by file bytes (jsnoop_partition_lpt), 1 = contiguous index ranges    */
+    int32_t  keep_resident;         /* 1: one round per shard, and every result's batch / image stay valid until jsnoop_job_clear / _destroy:
+                                       N DIBs resident across the devices.  jsnoop_job_run returns -1 before any decode if a shard needs more rounds */
+} JsnoopJobOptions;
+typedef struct JsnoopJobFile {
+    uint32_t struct_size;           /* jsnoop_job_file_result: set to sizeof(your JsnoopJobFile) (or 0: this header's); no byte past it is written */
+    int32_t  index;                 /* what jsnoop_job_add_file / _add_path returned                                                     */
+    int32_t  status;                /* JSNOOP_JOB_*                                                                                      */
+    int32_t  kind;                  /* 1 baseline, 2 progressive, 0 unknown (refused / unreadable)                                       */
+    int32_t  shard, device, round;  /* where and when it was decoded (round counts per shard from 0)                                     */
+    int32_t  image;                 /* index in `batch`                                                                                  */
+    JsnoopBatch* batch;             /* valid during the callback (with keep_resident: until clear / destroy), NULL otherwise.  Every per-image
+                                       jsnoop_batch_* call works on (batch, image): read_dib, dib_dev, log, side_outputs, export_tiff, color_stats */
+    uint32_t info16[16];            /* as jsnoop_batch_image_info                                                                        */
+    uint64_t dib_hash;              /* the word jsnoop_batch_dib_hashes gives for this image                                             */
+    const char* message;            /* "" or why the file was refused / unreadable; owned by the job, valid until clear / destroy / the next run */
+} JsnoopJobFile;
+typedef struct JsnoopJobStats {
+    uint32_t struct_size;           /* set by the caller like JsnoopJobFile's                                                            */
+    int32_t  files, ok, refused, unreadable;   /* files reported; ok + refused + unreadable == files                                     */
+    int32_t  flagged;               /* decoded files with any JSNOOP_FLAG_* raised                                                       */
+    int32_t  rounds;                /* rounds decoded, all shards                                                                        */
+    int32_t  nshards;
+    uint64_t pixels;                /* sum(SOF X*Y) of the decoded files                                                                 */
+    uint64_t dib_hash_sum;          /* sum of dib_hash mod 2^64: the same for every partition                                            */
+    uint64_t max_round_device_bytes;/* largest jsnoop_batch_device_bytes of a round's two batches                                        */
+    double   wall_ms;               /* jsnoop_job_run, start to return                                                                   */
+    double   shard_ms[JSNOOP_JOB_MAX_SHARDS];  /* busy time of each shard's thread                                                       */
+} JsnoopJobStats;
+/* The greedy longest-processing-time rule on its own (host only, no device needed): files in the order (cost descending, index ascending),
+ * each into the part with the least load so far, ties to the lowest part.  part_of[i] = part of file i.  0, or -1 for a bad argument.     */
+int        jsnoop_partition_lpt(const uint64_t* costs, int n, int parts, int* part_of);
+/* devices / nshards: the device of every shard (a device may be named more than once: logical shards on one GPU); NULL, 0 = one shard
+ * per visible device.  At most JSNOOP_JOB_MAX_SHARDS.  NULL + jsnoop_last_error() without a device (no CPU fallback) or on a bad list.  */
+JsnoopJob* jsnoop_job_create(const int* devices, int nshards);
+void       jsnoop_job_destroy(JsnoopJob*);
+void       jsnoop_job_options_defaults(JsnoopJobOptions* out);
+int        jsnoop_job_set_options(JsnoopJob*, const JsnoopJobOptions*);
+int        jsnoop_job_set_tuning(JsnoopJob*, const JsnoopTuning*);          /* handed to every batch the job creates                    */
+int        jsnoop_job_add_file(JsnoopJob*, const uint8_t* file, size_t len); /* bytes copied; returns the file index; content is not judged here */
+int        jsnoop_job_add_path(JsnoopJob*, const char* path);               /* read by the shard that owns it, in the round that decodes it */
+int        jsnoop_job_count(const JsnoopJob*);
+void       jsnoop_job_clear(JsnoopJob*);                                    /* drops files, results and resident batches                */
+typedef int (*jsnoop_job_file_fn)(void* user, const JsnoopJobFile* f);      /* non-zero return cancels the job                          */
+/* 0 = every file reported, 1 = cancelled by the callback (later files stay JSNOOP_JOB_PENDING), -1 = error.  on_file and stats may be NULL. */
+int        jsnoop_job_run(JsnoopJob*, jsnoop_job_file_fn on_file, void* user, JsnoopJobStats* stats);
+int        jsnoop_job_file_result(const JsnoopJob*, int index, JsnoopJobFile* out);
 
 #ifdef __cplusplus
 }

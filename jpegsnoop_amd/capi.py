@@ -21,6 +21,32 @@ class Tuning(C.Structure):
                 ("pg_lanes", C.c_int32), ("cross_checks", C.c_uint32), ("debug", C.c_uint32)]
 
 
+JOB_MAX_SHARDS = 16
+JOB_PENDING, JOB_OK, JOB_REFUSED, JOB_UNREADABLE = -1, 0, 1, 2
+
+
+class JobOptions(C.Structure):
+    """JsnoopJobOptions of include/jsnoop_gpu.h."""
+    _fields_ = [("struct_size", C.c_uint32), ("decode_ac", C.c_int32), ("want_planes", C.c_int32), ("enable_log", C.c_int32),
+                ("max_images_per_round", C.c_int32), ("max_round_bytes", C.c_uint64), ("partition", C.c_int32), ("keep_resident", C.c_int32)]
+
+
+class JobFile(C.Structure):
+    """JsnoopJobFile of include/jsnoop_gpu.h: the result of one file of a job."""
+    _fields_ = [("struct_size", C.c_uint32), ("index", C.c_int32), ("status", C.c_int32), ("kind", C.c_int32), ("shard", C.c_int32),
+                ("device", C.c_int32), ("round", C.c_int32), ("image", C.c_int32), ("batch", C.c_void_p), ("info16", C.c_uint32 * 16),
+                ("dib_hash", C.c_uint64), ("message", C.c_char_p)]
+
+
+class JobStats(C.Structure):
+    """JsnoopJobStats of include/jsnoop_gpu.h."""
+    _fields_ = [("struct_size", C.c_uint32), ("files", C.c_int32), ("ok", C.c_int32), ("refused", C.c_int32), ("unreadable", C.c_int32),
+                ("flagged", C.c_int32), ("rounds", C.c_int32), ("nshards", C.c_int32), ("pixels", C.c_uint64), ("dib_hash_sum", C.c_uint64),
+                ("max_round_device_bytes", C.c_uint64), ("wall_ms", C.c_double), ("shard_ms", C.c_double * JOB_MAX_SHARDS)]
+
+
+JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
+
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS = 1, 2, 4, 8, 16, 32
 DBG_CAND, DBG_CAND_LINKS, DBG_TAIL, DBG_TIMING = 1, 2, 4, 8
 
@@ -136,6 +162,19 @@ SIGNATURES = {
     "jsnoop_pipeline_slot": (_p, [_p, _i]),
     "jsnoop_pipeline_run": (_i, [_p, _i, _i, C.POINTER(C.c_double)]),
     "jsnoop_batch_pixels": (C.c_uint64, [_p]),
+    "jsnoop_batch_device_bytes": (C.c_uint64, [_p]),
+    "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
+    "jsnoop_job_create": (_p, [_PI, _i]),
+    "jsnoop_job_destroy": (None, [_p]),
+    "jsnoop_job_options_defaults": (None, [C.POINTER(JobOptions)]),
+    "jsnoop_job_set_options": (_i, [_p, C.POINTER(JobOptions)]),
+    "jsnoop_job_set_tuning": (_i, [_p, C.POINTER(Tuning)]),
+    "jsnoop_job_add_file": (_i, [_p, _p, _sz]),
+    "jsnoop_job_add_path": (_i, [_p, C.c_char_p]),
+    "jsnoop_job_count": (_i, [_p]),
+    "jsnoop_job_clear": (None, [_p]),
+    "jsnoop_job_run": (_i, [_p, JOB_FILE_FN, _p, C.POINTER(JobStats)]),
+    "jsnoop_job_file_result": (_i, [_p, _i, C.POINTER(JobFile)]),
 }
 
 _lib = None

@@ -14,7 +14,10 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <algorithm>
+#include <cctype>
 #include <cstdio>
+#include <filesystem>
 #include <functional>
 #include <stdexcept>
 #include <string>
@@ -275,9 +278,81 @@ public:
     bool     BatchGetSideOutputs(int nFileInd, uint32_t* pMcuFileMap, int16_t* pBlkDcY, int16_t* pBlkDcCb, int16_t* pBlkDcCr, uint32_t* pDhtHisto, unsigned* pStatus8, int* pBrightAvg10)
     { return jsnoop_batch_side_outputs(m_b, nFileInd, pMcuFileMap, pBlkDcY, pBlkDcCb, pBlkDcCr, pDhtHisto, pStatus8, pBrightAvg10) == 0; }
     bool     BatchExportTiff(int nFileInd, const std::string& strFname, int nMode = 0) { return jsnoop_batch_export_tiff(m_b, nFileInd, strFname.c_str(), nMode) == 0; }
+
+    // ---- the whole batch loop on every device: GenBatchFileList :454 builds the list, DoBatchFileProcess :765-845 works through it -- here as ONE job
+    //      (jsnoop_job_* of include/jsnoop_gpu.h): baseline and progressive files side by side, sharded over the devices, decoded in memory-bounded
+    //      rounds; a file the front end refuses or that cannot be read is noted and the loop moves on, as the reference's does (:794-798).
+    struct BatchFileInfo { std::string strSrc /*full path*/, strRel /*below dirSrc*/; };
+    // The file list of dirSrc (sub-folders with bRecSubdir), sorted by relative path; GenBatchFileListSingle's filter (:608-622): only names whose
+    // extension, lower-cased, is .jpg or .jpeg.  Returns the number of files listed.
+    unsigned GenBatchFileList(const std::string& dirSrc, bool bRecSubdir)
+    {
+        namespace fs = std::filesystem;
+        m_batchFiles.clear(); m_strBatchDirSrc = dirSrc;
+        std::error_code ec;
+        auto take = [&](const fs::directory_entry& de) {
+            if (!de.is_regular_file(ec)) return;
+            std::string ext = de.path().extension().string();
+            std::transform(ext.begin(), ext.end(), ext.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+            if (ext != ".jpg" && ext != ".jpeg") return;
+            m_batchFiles.push_back({ de.path().string(), de.path().lexically_relative(dirSrc).generic_string() });
+        };
+        if (bRecSubdir) { for (fs::recursive_directory_iterator it(dirSrc, fs::directory_options::skip_permission_denied, ec), end; !ec && it != end; it.increment(ec)) take(*it); }
+        else { for (fs::directory_iterator it(dirSrc, ec), end; !ec && it != end; it.increment(ec)) take(*it); }
+        std::sort(m_batchFiles.begin(), m_batchFiles.end(), [](const BatchFileInfo& a, const BatchFileInfo& b) { return a.strRel < b.strRel; });
+        return (unsigned)m_batchFiles.size();
+    }
+    unsigned GetBatchFileListCount() const { return (unsigned)m_batchFiles.size(); }
+    std::string GetBatchFileInfo(unsigned nFileInd) const { return nFileInd < m_batchFiles.size() ? m_batchFiles[nFileInd].strSrc : std::string(); }   // :686
+    const BatchFileInfo* GetBatchFileEntry(unsigned nFileInd) const { return nFileInd < m_batchFiles.size() ? &m_batchFiles[nFileInd] : nullptr; }
+
+    void     JobSetOptions(const JsnoopJobOptions& o) { m_jobOpt = o; m_bJobOpt = true; }
+    // Runs the listed files as one job over `devices` (empty: one shard per visible device); fn sees every file once, on this thread -- f.batch / f.image
+    // take the per-image jsnoop_batch_* calls while it runs.  A false return cancels.  Returns jsnoop_job_run's value (0 done, 1 cancelled, -1 error).
+    int      JobRun(const std::function<bool(const JsnoopJobFile&)>& fn, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr)
+    {
+        JsnoopJob* j = jsnoop_job_create(devices.empty() ? nullptr : devices.data(), (int)devices.size());
+        if (!j) return -1;
+        int rc = (m_bJobOpt && jsnoop_job_set_options(j, &m_jobOpt)) ? -1 : 0;
+        for (size_t i = 0; rc == 0 && i < m_batchFiles.size(); i++) if (jsnoop_job_add_path(j, m_batchFiles[i].strSrc.c_str()) < 0) rc = -1;
+        if (rc == 0) {
+            auto thunk = [](void* u, const JsnoopJobFile* f) -> int { return (*static_cast<const std::function<bool(const JsnoopJobFile&)>*>(u))(*f) ? 0 : 1; };
+            rc = jsnoop_job_run(j, fn ? static_cast<jsnoop_job_file_fn>(thunk) : nullptr, const_cast<void*>(static_cast<const void*>(&fn)), pStats);
+        }
+        jsnoop_job_destroy(j);
+        return rc;
+    }
+    // DoBatchFileProcess for every listed file at once.  With bWriteLog each file gets <dirDst>/<relative path>.txt, the name GenBatchFileListSingle derives
+    // (:649-650), holding what BatchLogSave writes: the DecodeScanImg report.  A progressive file has no such report (the reference refuses SOF2): the
+    // library's own wording of that goes in its place; a refused or unreadable file gets its message.  Returns the number of files decoded, or -1.
+    int      DoBatchFileProcessAll(bool bWriteLog, const std::string& dirDst, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr)
+    {
+        namespace fs = std::filesystem;
+        JsnoopJobOptions o; if (m_bJobOpt) o = m_jobOpt; else jsnoop_job_options_defaults(&o);
+        if (bWriteLog) { o.enable_log = 1; o.want_planes = 1; }                               // (the report quotes plane samples)
+        const JsnoopJobOptions saved = m_jobOpt; const bool bSaved = m_bJobOpt;
+        m_jobOpt = o; m_bJobOpt = true;
+        int nOk = 0;
+        const int rc = JobRun([&](const JsnoopJobFile& f) {
+            if (f.status == JSNOOP_JOB_OK) nOk++;
+            if (!bWriteLog || f.index < 0 || (size_t)f.index >= m_batchFiles.size()) return true;
+            const fs::path log = fs::path(dirDst) / (m_batchFiles[(size_t)f.index].strRel + ".txt");
+            std::error_code ec; fs::create_directories(log.parent_path(), ec);
+            FILE* fp = fopen(log.string().c_str(), "w");
+            if (!fp) return true;
+            auto thunk = [](void* u, int lvl, const char* txt) { fprintf(static_cast<FILE*>(u), "%s%s\n", lvl == 2 ? "E:" : lvl == 1 ? "W:" : "", txt); };
+            if (f.status != JSNOOP_JOB_OK) fprintf(fp, "E:%s\n", f.message);
+            else if (jsnoop_batch_log(f.batch, f.image, 0, 0, 0, thunk, fp)) fprintf(fp, "W:%s\n", jsnoop_last_error());
+            fclose(fp);
+            return true;
+        }, devices, pStats);
+        m_jobOpt = saved; m_bJobOpt = bSaved;
+        return rc < 0 ? -1 : nOk;
+    }
     CimgDecodeGpu* ImgDec() { return m_pImgDec; }
     JsnoopBatch* Handle() { return m_b; }
 private:
     CwindowBufView m_view; std::vector<uint8_t> m_file; std::string m_strPathName; bool m_bFileAnalyzed = false;
     CimgDecodeGpu* m_pImgDec; JsnoopBatch* m_b = nullptr;
+    std::vector<BatchFileInfo> m_batchFiles; std::string m_strBatchDirSrc; JsnoopJobOptions m_jobOpt{}; bool m_bJobOpt = false;
 };

@@ -530,6 +530,63 @@ int JsnoopBatch::upload()
     uploaded = true;
     return 0;
 }
+// What upload() asks hipMalloc for, for the images the batch holds now (jsnoop_batch_device_bytes): the sizing above restated without touching the device,
+// grow()'s slack included.  Where upload() chooses by job size (sub-sequence length, candidate synchronisation, MCUs per back-end wave) the largest of the
+// forms it may choose is counted, so the figure is never below the request and never falls when an image is added.  Not counted: scratch that only a
+// later request allocates (side-output passes, the one-image helper batch behind second attempts at damaged files).
+static uint64_t js_arena_bytes(const JsnoopBatch* b, int wl)
+{
+    auto g = [](uint64_t need) { return need + need / 16 + 256; };             // grow()
+    const uint64_t n = b->imgs.size(), sub_bytes = 4ull << wl;
+    uint64_t blocks = 0, dibb = 0, plane = 0, side = 0, ustr = 0, subs = 0, segw = 0, mcub = 0, usc = 0, wgs = 0, raw = b->raw_bytes;
+    const uint32_t mpw = b->tune.mcus_per_wave > 0 ? (uint32_t)b->tune.mcus_per_wave : 1u;     // (automatic: at least one MCU per wave)
+    for (const JsImage& im : b->imgs) {
+        const uint32_t nmcu = im.mcu_xmax * im.mcu_ymax;
+        blocks += im.total_blocks; dibb += align_up((uint64_t)im.img_x * im.img_y * 4, 256);
+        if (b->opt_want_planes) plane += align_up((uint64_t)im.blk_xmax * 8 * im.blk_ymax * 8 * 3, 64);
+        side += align_up(js_side_words(nmcu, im.blk_xmax * im.blk_ymax), 4);
+        const uint64_t ucap = align_up((uint64_t)im.scan_len + 64, 64ull * sub_bytes); ustr += ucap;
+        subs += align_up((ucap + sub_bytes - 1) / sub_bytes, 256);
+        const uint64_t want_seg = im.rst_interval ? (uint64_t)nmcu / im.rst_interval + 2 : 1;
+        segw += align_up(std::min<uint64_t>((1u << 20) - 1, want_seg * 2 + 16), 4);
+        mcub += align_up(nmcu, 16);
+        usc += std::max<uint64_t>(1, ((im.scan_start & 15) + (uint64_t)im.scan_len + JS_US_CHUNK - 1) / JS_US_CHUNK);
+        wgs += std::max(1u, (nmcu + 8 * mpw - 1) / (8 * mpw));
+    }
+    uint64_t t = g(raw + 64) + g(blocks * 128) + g(blocks * 2 + 64) + g(dibb) + g(side * 4) + g(n * sizeof(JsImage)) + g(std::max<uint64_t>(1, b->tables.size()) * sizeof(JsTableSet)) +
+                 g((n + 1) * 4) + g(n * 4) + g(n * 8) + 2 * g(ustr + 64) + g(subs * 24 + 64 + js_sync_list_words(subs, (uint32_t)n) * 4) + g(1024) + g(segw * 4 + 64) +
+                 2 * g(usc * 4 + 64) + 2 * g(2 * (n + 1) * 4) + g(mcub + 64) + g(JS_DC_PARTS_BYTES) + g(n * 8 + 64) + g(usc * 8 + 64) + g(wgs * 16 + 64) + 64 * 64 * sizeof(float);
+    if (b->opt_want_planes) t += g(plane * 2);
+    if (b->opt_events) t += g(n * (1 + (uint64_t)JS_EV_WORDS * JS_EV_MAX) * 4);
+    if (wl == 4 && b->tune.cand_rounds >= 0) {                                 // candidate synchronisation: up to the largest job that takes it
+        const uint64_t lanes = b->tune.cand_max_walks ? b->tune.cand_max_walks : 2600000;
+        t += g(js_cand_bytes(std::min<uint64_t>(subs, lanes + 512 * n))) + g(n * JS_CAND_REQ_WORDS * 4);
+    }
+    return t;
+}
+uint64_t js_batch_device_bytes(const JsnoopBatch* b)
+{
+    if (!b || b->imgs.empty()) return 0;
+    uint64_t most = 0;
+    if (b->tune.sub_wl) most = js_arena_bytes(b, b->tune.sub_wl);
+    else for (int wl = 4; wl <= 7; wl++) most = std::max(most, js_arena_bytes(b, wl));
+    return most + js_prog_device_bytes(b);
+}
+// The batch as it was before its last add (the job layer closes a round on the image that would pass its budget): adds only append.
+JsBatchMark js_batch_mark(const JsnoopBatch* b)
+{
+    JsBatchMark m; m.nimg = b->imgs.size(); m.ntables = b->tables.size(); m.nhinfo = b->hinfo.size(); m.raw_bytes = b->raw_bytes;
+    js_prog_mark(b, m.prog);
+    return m;
+}
+void js_batch_rewind(JsnoopBatch* b, const JsBatchMark& m)
+{
+    if (b->imgs.size() > m.nimg) b->imgs.resize(m.nimg);
+    if (b->tables.size() > m.ntables) b->tables.resize(m.ntables);
+    if (b->hinfo.size() > m.nhinfo) b->hinfo.resize(m.nhinfo);
+    b->raw_bytes = m.raw_bytes; b->uploaded = false;
+    js_prog_rewind(b, m.prog);
+}
 static const char* kStageName[JSNOOP_NUM_STAGES] = { "clear", "unstuff", "sync", "blockscan", "write", "dcscan", "exact", "idct_color" };
 
 int JsnoopBatch::decode(bool timed)
@@ -1147,6 +1204,7 @@ uint64_t jsnoop_batch_algorithmic_bytes(const JsnoopBatch* b)
 { uint64_t s = 0; for (const JsImage& im : b->imgs) s += (uint64_t)im.scan_len + (uint64_t)im.img_x * im.img_y * 4; return s; }
 uint64_t jsnoop_batch_pixels(const JsnoopBatch* b)
 { uint64_t s = 0; for (const JsImage& im : b->imgs) s += (uint64_t)im.dim_x * im.dim_y; return s; }
+uint64_t jsnoop_batch_device_bytes(const JsnoopBatch* b) { return js_batch_device_bytes(b); }
 
 } // extern "C"
 

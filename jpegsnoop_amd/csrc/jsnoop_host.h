@@ -193,3 +193,11 @@ void js_prog_dirty(JsnoopBatch* b);
 void js_prog_free(JsnoopBatch* b);
 void js_prog_dup(JsnoopBatch* b, uint32_t src, uint32_t dst);
 bool js_is_progressive(const uint8_t* file, size_t len);               // first SOF marker of the stream is SOF2
+// what the job layer (jsnoop_job.cpp) needs of a batch: the HBM upload() requests for it, and taking the last add back
+struct JsBatchMark { size_t nimg, ntables, nhinfo; uint64_t raw_bytes; size_t prog[5]; };
+uint64_t js_batch_device_bytes(const JsnoopBatch* b);                  // jsnoop_host.cpp
+JsBatchMark js_batch_mark(const JsnoopBatch* b);
+void js_batch_rewind(JsnoopBatch* b, const JsBatchMark& m);
+uint64_t js_prog_device_bytes(const JsnoopBatch* b);                   // jsnoop_progressive.cpp: the table / interval / work-list buffer
+void js_prog_mark(const JsnoopBatch* b, size_t* m5);
+void js_prog_rewind(JsnoopBatch* b, const size_t* m5);

@@ -247,6 +247,28 @@ void js_prog_dup(JsnoopBatch* b, uint32_t src, uint32_t dst)
     g->dirty = true;
 }
 
+// the layout of js_prog_upload's buffer, shared with js_prog_device_bytes
+static size_t js_prog_buf_bytes(const JsProgBatch* g)
+{
+    const size_t nimg = g->frames.size(), nsc = g->scans.size();
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    return up(nimg * sizeof(JsProgFrame)) + up(nsc * sizeof(JsProgScan)) + up(g->tabs.size() * sizeof(JsProgTable)) + up(g->segs.size() * sizeof(JsProgSeg)) +
+           up(nimg * 16) + up(nsc * 4) + up((nsc + (size_t)g->nlev) * 4) + up((nimg + 1) * 4);
+}
+uint64_t js_prog_device_bytes(const JsnoopBatch* b) { return js_prog_count(b) ? (uint64_t)js_prog_buf_bytes(b->prog) * 2 : 0; }   // (js_prog_upload allocates twice the layout)
+void js_prog_mark(const JsnoopBatch* b, size_t* m)
+{
+    const JsProgBatch* g = b->prog;
+    m[0] = g ? g->frames.size() : 0; m[1] = g ? g->scans.size() : 0; m[2] = g ? g->tabs.size() : 0; m[3] = g ? g->segs.size() : 0; m[4] = g ? (size_t)g->nlev : 0;
+}
+void js_prog_rewind(JsnoopBatch* b, const size_t* m)
+{
+    JsProgBatch* g = b->prog;
+    if (!g || g->frames.size() <= m[0]) return;
+    g->frames.resize(m[0]); g->scans.resize(m[1]); g->level.resize(m[1]); g->tabs.resize(m[2]); g->segs.resize(m[3]); g->nlev = (int)m[4];
+    g->first_scan.resize(m[0] ? m[0] + 1 : 0); g->dirty = true;
+}
+
 int JsnoopBatch::add_progressive(JsnoopDecoder* d, const uint8_t* f, size_t n)
 {
     if (imgs.size() != js_prog_count(this)) { js_set_error("a batch holds either baseline or progressive files, not both"); return -1; }

@@ -272,6 +272,9 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_export_tiff(self._h, i, path.encode(), mode), "batch_export_tiff")
 
     def algorithmic_bytes(self): return int(self._lib.jsnoop_batch_algorithmic_bytes(self._h))
+    def device_bytes(self):
+        """HBM that upload() requests for the images the batch holds now (jsnoop_batch_device_bytes)."""
+        return int(self._lib.jsnoop_batch_device_bytes(self._h))
     def pixels(self): return int(self._lib.jsnoop_batch_pixels(self._h))
 
 
@@ -301,6 +304,124 @@ class JpegPipeline:
             for b in self.slots:
                 b._h = None                      # owned by the pipeline
             self._lib.jsnoop_pipeline_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_INFO_KEYS = "dim_x dim_y img_x img_y mcu_w mcu_h mcu_xmax mcu_ymax blk_xmax blk_ymax scan_bytes flags path ncomp file_len total_blocks".split()
+
+
+class JobFileResult:
+    """One file of a JpegJob: status ("ok" / "refused" / "unreadable" / "pending"), kind ("baseline" / "progressive" / None), where it was
+    decoded, info (as JpegBatch.info), dib_hash, message.  `batch` / `image` address the file in a borrowed JpegBatch: inside the callback,
+    or until JpegJob.clear() / close() with keep_resident; None otherwise."""
+    STATUS = {capi.JOB_PENDING: "pending", capi.JOB_OK: "ok", capi.JOB_REFUSED: "refused", capi.JOB_UNREADABLE: "unreadable"}
+    KIND = {0: None, 1: "baseline", 2: "progressive"}
+
+    def __init__(self, lib, f: "capi.JobFile", want_planes: bool):
+        self.index, self.status, self.kind = f.index, self.STATUS[f.status], self.KIND[f.kind]
+        self.shard, self.device, self.round, self.image = f.shard, f.device, f.round, f.image
+        self.info = dict(zip(_INFO_KEYS, f.info16))
+        self.dib_hash = int(f.dib_hash)
+        self.message = (f.message or b"").decode(errors="replace")
+        self.batch = None
+        if f.batch:
+            b = JpegBatch.__new__(JpegBatch)
+            b._lib, b._h, b.want_planes, b._borrowed = lib, f.batch, want_planes, True
+            self.batch = b
+
+    def __repr__(self):
+        return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
+
+
+class JpegJob:
+    """One call decodes a mixed file list (baseline and progressive, good and bad) over all devices: jsnoop_job_* of include/jsnoop_gpu.h,
+    the whole-node form of CJPEGsnoopCore::DoBatchFileProcess (source/JPEGsnoopCore.cpp:765-845).
+
+    devices: the device of every shard (a device may appear more than once: logical shards on one GPU); None = one shard per visible device.
+    Every file gets a result; a file the front end refuses or a path that cannot be read never fails the job."""
+
+    def __init__(self, devices=None, decode_ac=True, want_planes=False, enable_log=False, max_images_per_round=0, max_round_bytes=0,
+                 partition="lpt", keep_resident=False, tuning=None):
+        self._lib = capi.load()
+        if devices is None:
+            self._h = self._lib.jsnoop_job_create(None, 0)
+        else:
+            devs = (C.c_int * len(devices))(*devices)
+            self._h = self._lib.jsnoop_job_create(devs, len(devices))
+        if not self._h:
+            raise RuntimeError("jsnoop_job_create failed: " + capi.last_error())
+        o = capi.JobOptions()
+        self._lib.jsnoop_job_options_defaults(C.byref(o))
+        o.decode_ac, o.want_planes, o.enable_log = int(decode_ac), int(want_planes), int(enable_log)
+        o.max_images_per_round, o.max_round_bytes = int(max_images_per_round), int(max_round_bytes)
+        o.partition, o.keep_resident = {"lpt": 0, "contiguous": 1}[partition], int(keep_resident)
+        self._chk(self._lib.jsnoop_job_set_options(self._h, C.byref(o)), "job_set_options")
+        if tuning:
+            t = capi.Tuning(); self._lib.jsnoop_tuning_defaults(C.byref(t))
+            for k, v in tuning.items():
+                if not hasattr(t, k): raise AttributeError("JsnoopTuning has no field " + k)
+                setattr(t, k, v)
+            self._chk(self._lib.jsnoop_job_set_tuning(self._h, C.byref(t)), "job_set_tuning")
+        self.want_planes = bool(want_planes)
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RuntimeError(f"{what} failed: {capi.last_error()}")
+        return rc
+
+    def add(self, data: bytes) -> int:
+        """Adds one file image (bytes copied; the content is judged when the job runs).  Returns the file index."""
+        buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+        return self._chk(self._lib.jsnoop_job_add_file(self._h, C.cast(buf, C.c_void_p), len(data)), "job_add_file")
+
+    def add_path(self, path) -> int:
+        """Adds a file by path: read by the shard that owns it, in the round that decodes it."""
+        import os
+        return self._chk(self._lib.jsnoop_job_add_path(self._h, os.fsencode(path)), "job_add_path")
+
+    def __len__(self): return self._lib.jsnoop_job_count(self._h)
+    def clear(self): self._lib.jsnoop_job_clear(self._h)
+
+    def run(self, on_file=None) -> dict:
+        """Decodes every file.  on_file(result) is called on this thread, once per file; a true return value cancels the job.
+        Returns the job's statistics (JsnoopJobStats as a dict, plus "cancelled")."""
+        err = []
+
+        def thunk(_user, fp):
+            try:
+                return 1 if on_file(JobFileResult(self._lib, fp.contents, self.want_planes)) else 0
+            except BaseException as e:                   # (no exception crosses the C ABI: cancel, re-raise behind the run)
+                err.append(e)
+                return 1
+        cb = capi.JOB_FILE_FN(thunk) if on_file is not None else C.cast(None, capi.JOB_FILE_FN)
+        st = capi.JobStats(); st.struct_size = C.sizeof(capi.JobStats)
+        rc = self._lib.jsnoop_job_run(self._h, cb, None, C.byref(st))
+        if err:
+            raise err[0]
+        self._chk(rc, "job_run")
+        out = {k: getattr(st, k) for k in ("files", "ok", "refused", "unreadable", "flagged", "rounds", "nshards", "pixels", "dib_hash_sum",
+                                           "max_round_device_bytes", "wall_ms")}
+        out["shard_ms"] = list(st.shard_ms)[: st.nshards]
+        out["cancelled"] = rc == 1
+        return out
+
+    def result(self, i) -> JobFileResult:
+        f = capi.JobFile(); f.struct_size = C.sizeof(capi.JobFile)
+        self._chk(self._lib.jsnoop_job_file_result(self._h, i, C.byref(f)), "job_file_result")
+        return JobFileResult(self._lib, f, self.want_planes)
+
+    def results(self) -> list:
+        return [self.result(i) for i in range(len(self))]
+
+    def close(self):
+        if self._h:
+            self._lib.jsnoop_job_destroy(self._h)
             self._h = None
 
     def __del__(self):
