@@ -626,19 +626,26 @@ __device__ __forceinline__ PairList pair_list(const void* mem, uint32_t lane)
     L.l8 = l * 8u; L.row0 = (2u * l) << 8;
     return L;
 }
-// The rounds are generated text (tools/gen/gen_pair_round.py -> jsnoop_pair_round.h): sixteen steps, every step leaves when the longer list
-// has no such term (the scalar unit is nearly idle in this form: two scalar instructions per step are free); what is fetched past the end
-// of the lists is dropped behind the last step.  Round 6: the coefficient of a term no longer rides on the two multiplies as a DPP operand
+// The rounds are generated text (tools/gen/gen_pair_round.py -> jsnoop_pair_round.h): sixteen steps, every step asks whether the longer list
+// still has the term it is about to fetch for (the scalar unit is nearly idle in this form: two scalar instructions per step are free).
+// Round 6: the coefficient of a term no longer rides on the two multiplies as a DPP operand
 // (v_mul_f32_dpp issues in 4.2 cycles, v_mul_f32 in 2.2: profiles/r04_instr_rates.txt) -- the coefficients of two consecutive terms come as
 // ONE ds_read_b64 that every lane of a half aims at the same eight bytes of its list (a broadcast: one LDS cycle per half), three such pairs
 // in flight; a step is then 13 vector cycles (two multiplies, two adds, the DPP address add) and 1.5 LDS instructions where it was 17 and 1
 // (tools/probes/idct_bcast.hip, profiles/r06_term_loop.txt).  Registers: five table pairs v[54:63] (four reads in flight), three
 // coefficient pairs v[48:53] -- fixed, inline asm cannot name the halves of a 64-bit operand.
 #include "jsnoop_pair_round.h"
-#define PAIR_ROUND(R)                                                                                                            \
-    asm volatile(PAIR_ROUND_ASM_##R                                                                                              \
-        : [acc0] "+v"(acc0), [acc1] "+v"(acc1), [ad] "=&v"(ad), [rw] "=&v"(rw)                                                   \
-        : [ah] "v"(L.a_half), [arw] "v"(L.a_rw), [l8] "v"(L.l8), [nl] "s"(nl) : "scc", PAIR_ROUND_CLOBBERS)
+// Round 7: the EXACT form (PAIR_EXACT_ASM, gen_exact).  Up to round 6 a round (the header's four per-round texts, kept for the variant builds)
+// fetched the table pair of step s + 4 and the coefficient pair of steps s + 4, s + 5 before it knew that those steps exist, and dropped them
+// at the exit: three of the five rounds of a 4:2:0 MCU leave early, four v_add_u32_dpp + ds_read_b64 (512 bytes each) and a broadcast read or
+// two thrown away each time.  The exact form compares against s + 4: the first step that fails finds nl == s + 4, and a generated tail
+// finishes the four steps in flight with no further read and the wait counts of its own queue; lists shorter than four terms have a prologue
+// per length.  One text serves all four rounds (the list address moves on by 64 bytes: `ah` is a copy): a pair is 460 instructions where the
+// four rounds were 620.  Same steps, same multiplies and adds in the same order (tests/test_pair_round_exact.py replays every length).
+#define PAIR_ROUNDS()                                                                                                            \
+    asm volatile(PAIR_EXACT_ASM                                                                                                  \
+        : [acc0] "+v"(acc0), [acc1] "+v"(acc1), [ad] "=&v"(ad), [rw] "=&v"(rw), [ah] "+v"(ah), [nl] "+s"(nl), [ro] "+s"(ro)      \
+        : [arw] "v"(L.a_rw), [l8] "v"(L.l8) : "scc", PAIR_ROUND_CLOBBERS)
 
 // d: the lane's two coefficients, c[2l] | c[2l+1] << 16 (DC and, in DC-only mode, everything already masked out).
 // Returns in acc0 / acc1 the sums (x 2, see idct_run) of the lane's samples 2l and 2l+1 of its block.
@@ -664,11 +671,8 @@ __device__ __forceinline__ void idct_pair(uint32_t d, const PairList L, uint32_t
         const uint32_t w0 = L.a_half + (s0 << 2), w1 = L.a_half + (s1 << 2);
         lds_w32(w0, cf0); lds_w32(w0 + 256u, L.row0); lds_w32(w1, cf1); lds_w32(w1 + 256u, L.row0 + 256u);      // (in this order the compiler pairs them: two ds_write2st64_b32)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        uint32_t ad, rw;
-        { const uint32_t nl = n; PAIR_ROUND(0); }
-        if (n > 16) { const uint32_t nl = n - 16; PAIR_ROUND(1); }
-        if (n > 32) { const uint32_t nl = n - 32; PAIR_ROUND(2); }
-        if (n > 48) { const uint32_t nl = n - 48; PAIR_ROUND(3); }
+        uint32_t ad, rw, ah = L.a_half, nl = n, ro = 0;
+        PAIR_ROUNDS();
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }

@@ -14,18 +14,19 @@ run_lib() {
                "SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_SMEM SQ_INST_CYCLES_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_IFETCH SQ_LDS_BANK_CONFLICT" \
                "SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_INST_LEVEL_SMEM SQ_IFETCH_LEVEL SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT"; do
     i=$((i+1))
-    timeout 240 rocprofv3 --pmc $GROUP --kernel-trace --kernel-include-regex "$RE" --output-format csv -d $OUT/$NAME/p$i -o p$i -- python $ROOT/bench.py $ARGS > $OUT/$NAME/p$i.log 2>&1
+    timeout 240 rocprofv3 --pmc $GROUP --kernel-trace --kernel-include-regex "$RE" --output-format csv -d $OUT/$NAME/p$i -o p$i -- python $ROOT/bench.py $ARGS > $OUT/$NAME/p$i.log 2>&1 || return 1      # (a pass that fails or runs out of time ends the call: nothing more is started on the GPU)
   done
   python $ROOT/tools/pmc_summarize.py $OUT/$NAME > $OUT/$NAME/summary.txt 2>&1
-  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$NAME/st -o st -- python $ROOT/bench.py $ARGS > $OUT/$NAME/st.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$NAME/st -o st -- python $ROOT/bench.py $ARGS > $OUT/$NAME/st.log 2>&1 || return 1
   find $OUT/$NAME/st -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/$NAME/kernel_stats.csv
   rm -rf $OUT/$NAME/st $OUT/$NAME/p?/*/*_agent_info.csv
 }
-run_lib tree
+run_lib tree || { echo "a pass failed: stopped"; exit 1; }
 for SO in "$@"; do
   N=$(basename $SO .so)
   cp $ROOT/jpegsnoop_amd/libjsnoop_gpu.so /tmp/libjsnoop_gpu.orig.so; cp $ROOT/$SO $ROOT/jpegsnoop_amd/libjsnoop_gpu.so
-  run_lib $N
+  run_lib $N; RC=$?
   cp /tmp/libjsnoop_gpu.orig.so $ROOT/jpegsnoop_amd/libjsnoop_gpu.so
+  [ $RC = 0 ] || { echo "a pass failed: stopped"; exit 1; }
 done
 for d in $OUT/*/; do echo "== $d"; grep -A40 "$RE" $d/summary.txt | head -45; grep "$RE" $d/kernel_stats.csv | cut -c1-40,200-330; done
