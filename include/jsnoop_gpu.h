@@ -267,6 +267,7 @@ typedef struct JsnoopTuning {
 #define JSNOOP_XC_SIDE_EXACT      0x08u  /* side outputs always from the exact-mirror reader                                          */
 #define JSNOOP_XC_CAND_VERIFY     0x10u  /* k_sync's verification mode behind every candidate chain                                   */
 #define JSNOOP_XC_UNSTUFF_3PASS   0x20u  /* un-stuffing as count / scan / write passes instead of the fused look-back pass            */
+#define JSNOOP_XC_DC_GENERIC      0x40u  /* DC-only decodes through the Full-IDCT kernels instead of the DC-only fast form            */
 #define JSNOOP_DBG_CAND           0x01u  /* candidate chain: rounds, queued walks                                                     */
 #define JSNOOP_DBG_CAND_LINKS     0x02u  /* ... and the links left open per image (stops the stream)                                  */
 #define JSNOOP_DBG_TAIL           0x04u  /* damaged files: tail take-over decisions                                                   */
@@ -283,6 +284,18 @@ int          jsnoop_batch_count(const JsnoopBatch*);
 int          jsnoop_batch_upload(JsnoopBatch*);      /* pinned host -> HBM (async), builds device descriptors */
 int          jsnoop_batch_decode(JsnoopBatch*);      /* HBM -> HBM, asynchronous on the batch stream          */
 int          jsnoop_batch_sync(JsnoopBatch*);        /* waits; then re-decodes flagged images on the exact path */
+/* DC-only fast form.  DC-only (decode_ac = 0, what a single-image call with bDisplay = FALSE forces) is the reference's default mode: it parses the AC
+ * symbols without storing them and never runs the IDCT, so every sample of a block is its cumulative DC.  A decode takes a form of its own for that --
+ * a write pass without the coefficient arena and a back end straight from cumulative DC to DIB -- when EVERY image of the batch is DC-only, has one of
+ * the common layouts (three components, 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0) in the default preview mode without YCC shift and decode tables the parallel
+ * path takes, the exact path is not forced, and the decode records no events: a log callback (jsnoop_set_log_callback) and jsnoop_batch_enable_log keep a decode
+ * on the Full-IDCT kernels, as do JSNOOP_XC_DC_GENERIC and the cross-checks that name one of those kernels (JSNOOP_XC_WRITE_V1, _BACKEND_GENERIC).
+ * Results are the same bit for bit.  After such a decode the coefficient arena does not hold its blocks: whatever reads it (jsnoop_batch_read_coefs, a
+ * preview re-render, the repair of a damaged file at jsnoop_batch_sync) first decodes the batch again through the Full-IDCT kernels.
+ * jsnoop_batch_last_form: the form behind the results the batch holds NOW -- 0 = nothing decoded, 1 = Full-IDCT kernels, 2 = DC-only fast form (so 1
+ * after such a second decode); jsnoop_last_form: the same for the private batch behind a single-image decoder.                                       */
+int          jsnoop_batch_last_form(const JsnoopBatch*);
+int          jsnoop_last_form(JsnoopDecoder*);
 /* Timed decode: `reps` decodes bracketed by hipEvents on the batch stream; per-stage
  * average milliseconds into stage_ms[JSNOOP_NUM_STAGES] (may be NULL).  Returns the
  * average milliseconds per whole decode, < 0 on error.                              */

@@ -47,7 +47,7 @@ class JobStats(C.Structure):
 
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
-XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS = 1, 2, 4, 8, 16, 32
+XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
 DBG_CAND, DBG_CAND_LINKS, DBG_TAIL, DBG_TIMING = 1, 2, 4, 8
 
 _u, _i, _p, _sz = C.c_uint, C.c_int, C.c_void_p, C.c_size_t
@@ -142,6 +142,8 @@ SIGNATURES = {
     "jsnoop_batch_upload": (_i, [_p]),
     "jsnoop_batch_decode": (_i, [_p]),
     "jsnoop_batch_sync": (_i, [_p]),
+    "jsnoop_batch_last_form": (_i, [_p]),
+    "jsnoop_last_form": (_i, [_p]),
     "jsnoop_batch_decode_timed": (C.c_double, [_p, _i, C.POINTER(C.c_double)]),
     "jsnoop_stage_name": (C.c_char_p, [_i]),
     "jsnoop_batch_image_info": (_i, [_p, _i, _PU]),

@@ -180,7 +180,7 @@ const JsnoopTuning& js_env_tuning()
         { const long long sp = num("JSNOOP_SPLIT", 0); t.split = (sp == 1 || sp == 2) ? (int32_t)sp : 0; }
         t.mcus_per_wave = (int32_t)std::max<long long>(0, num("JSNOOP_MPW", 0));
         { const long long v = num("JSNOOP_PG_LANES", 0); t.pg_lanes = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 64) ? (int32_t)v : 0; }
-        t.cross_checks = (on("JSNOOP_BACKEND_GENERIC") ? JSNOOP_XC_BACKEND_GENERIC : 0u) | (on("JSNOOP_WRITE_V1") ? JSNOOP_XC_WRITE_V1 : 0u) | (on("JSNOOP_NO_TAIL") ? JSNOOP_XC_NO_TAIL : 0u) |
+        t.cross_checks = (on("JSNOOP_DC_GENERIC") ? JSNOOP_XC_DC_GENERIC : 0u) | (on("JSNOOP_BACKEND_GENERIC") ? JSNOOP_XC_BACKEND_GENERIC : 0u) | (on("JSNOOP_WRITE_V1") ? JSNOOP_XC_WRITE_V1 : 0u) | (on("JSNOOP_NO_TAIL") ? JSNOOP_XC_NO_TAIL : 0u) |
                          (on("JSNOOP_SIDE_EXACT") ? JSNOOP_XC_SIDE_EXACT : 0u) | (on("JSNOOP_CAND_VERIFY") ? JSNOOP_XC_CAND_VERIFY : 0u) |
                          (on("JSNOOP_UNSTUFF_3PASS") ? JSNOOP_XC_UNSTUFF_3PASS : 0u);
         const long long dc = num("JSNOOP_DEBUG_CAND", 0);
@@ -316,7 +316,7 @@ int JsnoopBatch::ensure_aux()
 }
 void JsnoopBatch::clear()
 {
-    imgs.clear(); hinfo.clear(); tables.clear(); raw_bytes = 0; uploaded = false; host_flags.clear(); side_done.clear(); side_mode.clear(); side_anoms.clear(); side_chunk_ok.clear(); side_events.clear(); side_pre.clear();
+    imgs.clear(); hinfo.clear(); tables.clear(); raw_bytes = 0; uploaded = false; last_form = 0; host_flags.clear(); side_done.clear(); side_mode.clear(); side_anoms.clear(); side_chunk_ok.clear(); side_events.clear(); side_pre.clear();
     js_prog_clear(this);
 }
 int JsnoopBatch::reserve_pinned(size_t need)
@@ -527,7 +527,7 @@ int JsnoopBatch::upload()
     h_us_base.assign(usb.begin(), usb.begin() + n + 1); h_us4_base.assign(usb.begin() + n + 1, usb.end()); h_sy_base.assign(syb.begin(), syb.begin() + n + 1); h_sn_base.assign(syb.begin() + n + 1, syb.end()); h_wg_base = wg;
     // two halves on two streams: by default from JS_SPLIT_FROM_BYTES of scan data on (above)
     split_parts = (n >= 2 && (tune.split == 2 || (tune.split == 0 && scan_total >= JS_SPLIT_FROM_BYTES))) ? 2 : 1;
-    uploaded = true;
+    uploaded = true; last_form = 0;                                // (the arenas were laid out anew: no decode's results in them)
     return 0;
 }
 // What upload() asks hipMalloc for, for the images the batch holds now (jsnoop_batch_device_bytes): the sizing above restated without touching the device,
@@ -594,6 +594,7 @@ int JsnoopBatch::decode(bool timed)
     HIP_TRY(hipSetDevice(device));
     if (!uploaded && upload()) return -1;
     const uint32_t n = (uint32_t)imgs.size();
+    last_form = (!force_generic && dc_fast_applies()) ? 2 : 1;     // (js_parallel_entropy_part and launch_back_end_part choose their kernels by it)
     side_done.assign(n, 0); side_mode.assign(n, 0); side_anoms.assign(n, std::vector<uint32_t>()); side_chunk_ok.assign(n, 0); side_events.assign(n, std::vector<uint32_t>()); side_pre.assign(n, 0); side_requests = 0;   // (nothing of an earlier decode's side pass survives)
     JsRange r_("jsnoop:decode (enqueue)");
     if (js_prog_count(this)) return decode_progressive(timed);     // SOF2 files: every scan of every image, one launch per dependency level
@@ -642,9 +643,39 @@ int JsnoopBatch::decode(bool timed)
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// DC-only fast form: every image DC-only with a fast layout (default preview, no YCC shift) and tables in the LUT form, nothing that wants the
+// generic kernels' by-products (event records, recorded MCU positions) and no cross-check that names a generic kernel.
+bool JsnoopBatch::dc_fast_applies() const
+{
+    if (opt_force_exact || is_helper || js_prog_count(this) || rec_pos || imgs.empty()) return false;
+    if (event_words && !private_no_log) return false;
+    if (tune.cross_checks & (JSNOOP_XC_DC_GENERIC | JSNOOP_XC_WRITE_V1 | JSNOOP_XC_BACKEND_GENERIC)) return false;
+    for (const JsImage& im : imgs) if (im.decode_ac || !js_dc_fast_order(im) || im.tableset >= tables.size() || !tables[im.tableset].lut_ok) return false;
+    return true;
+}
+int JsnoopBatch::redecode_generic()
+{
+    force_generic = true; const int rc = decode(false); force_generic = false;
+    if (rc) return -1;
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+int JsnoopBatch::ensure_generic()
+{
+    if (last_form != 2) return 0;
+    if (redecode_generic()) return -1;
+    return js_parallel_fixup(this);
+}
 int JsnoopBatch::launch_back_end(uint32_t nimg) { return launch_back_end_part(stream, 0, nimg); }
 int JsnoopBatch::launch_back_end_part(hipStream_t st, uint32_t i0, uint32_t nimg)
 {
+    if (last_form == 2) {                                         // DC-only fast form: cumulative DC -> DIB (k_dc_color), same workgroup partition and status reduction
+        const uint32_t wgs2 = h_wg_base.size() > i0 + nimg ? h_wg_base[i0 + nimg] - h_wg_base[i0] : total_wgs;
+        uint32_t most2 = 0; for (uint32_t i = i0; i < i0 + nimg && i + 1 < h_wg_base.size(); i++) most2 = std::max(most2, h_wg_base[i + 1] - h_wg_base[i]);
+        if (js_launch_dc_color(st, dev.imgs + i0, dev.wg_base + i0, nimg, wgs2, dev.dccum, dev.dib, dev.planes, dev.side, most2 > 64 ? dev.wg_part : nullptr)) {
+            js_set_error("DC-only back end launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
+        return 0;
+    }
     uint32_t tile = 16; int layout = -1;                          // layout: the one fast layout all images of the launch share, else 0
     for (uint32_t i = i0; i < i0 + nimg && i < imgs.size(); i++) {
         tile = std::max(tile, js_tile_bytes(imgs[i]));
@@ -824,6 +855,7 @@ void jsnoop_decode_scan_img(JsnoopDecoder* d, const uint8_t* file, size_t len, u
     JsnoopBatch* b = d->batch;
     b->clear();
     b->opt_decode_ac = d->opt_decode_ac;
+    b->private_no_log = d->log_fn == nullptr;                      // (no callback: nobody asks for the decode's event records)
     d->last_path = 0; d->last_flags = 0;
     const bool dbg_t = (b->tune.debug & JSNOOP_DBG_TIMING) != 0;   // where a call's wall time goes (stderr, one line per call)
     auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1068,6 +1100,8 @@ int jsnoop_batch_count(const JsnoopBatch* b) { return (int)b->imgs.size(); }
 int jsnoop_batch_upload(JsnoopBatch* b) { return b->upload(); }
 int jsnoop_batch_decode(JsnoopBatch* b) { return b->decode(false); }
 int jsnoop_batch_sync(JsnoopBatch* b) { return b->sync(); }
+int jsnoop_batch_last_form(const JsnoopBatch* b) { return b ? b->last_form : 0; }
+int jsnoop_last_form(JsnoopDecoder* d) { return d && d->batch ? d->batch->last_form : 0; }
 const char* jsnoop_stage_name(int s) { return s >= 0 && s < JSNOOP_NUM_STAGES ? kStageName[s] : ""; }
 double jsnoop_batch_decode_timed(JsnoopBatch* b, int reps, double* stage_ms)
 {
@@ -1105,6 +1139,7 @@ int jsnoop_batch_read_coefs(JsnoopBatch* b, int i, int16_t* dst, size_t max_bloc
     if (i < 0 || (size_t)i >= b->imgs.size()) return -1;
     const JsImage& im = b->imgs[i]; size_t nb = std::min<size_t>(max_blocks, im.total_blocks);
     HIP_TRY(hipSetDevice(b->device));
+    if (b->ensure_generic()) return -1;                           // (a DC-only fast-form decode left the arena untouched)
     if (b->d2h_staged(dst, b->dev.coef + im.coef_off * 64, nb * 128)) return -1;
     return (int)nb;
 }
@@ -1293,9 +1328,18 @@ void JsnoopDecoder::fetch_side()
     }
     if (!ok) log(2, "*** ERROR: reading the side block back failed: %s", g_err.c_str());
 }
+void JsnoopDecoder::arena_generic()
+{
+    JsnoopBatch* b = batch;
+    if (!have_image || !b || b->last_form != 2) return;
+    if (b->ensure_generic()) { log(2, "*** ERROR: device decode failed: %s", g_err.c_str()); return; }
+    if ((size_t)img < b->host_path.size()) { last_path = (int)b->host_path[img]; last_flags = b->host_flags[img]; }
+    side_ready = last_path == 2; report_cache = false; host_valid = 0;     // (the decode cleared the side block: what was fetched is an earlier decode's)
+}
 void JsnoopDecoder::rerender()                                  // CalcChannelPreview :4965 on the retained data: colour kernel only
 {
     if (!have_image) return;
+    arena_generic();                                               // the colour kernel reads the coefficient arena
     JsnoopBatch* b = batch; JsImage& im = b->imgs[0];
     im.preview_mode = preview_mode; im.shift_y = shift_y; im.shift_cb = shift_cb; im.shift_cr = shift_cr; im.shift_mcu_x = shift_mcu_x; im.shift_mcu_y = shift_mcu_y;
     hipSetDevice(b->device);

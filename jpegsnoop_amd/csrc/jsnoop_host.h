@@ -58,6 +58,7 @@ struct JsnoopDecoder {
     void ensure_side();      // side outputs are produced on first request when the parallel path decoded the image
     bool side_ready;
     void rerender();
+    void arena_generic();    // before anything reads the coefficient arena: a DC-only fast-form decode is repeated in the generic form (JsnoopBatch::ensure_generic)
     // bHistoEn / bStatClipEn statistics (m_sHisto, m_sStatClip, m_anCcHisto_*, m_anHistoYFull): cleared by DecodeScanImg
     // (:3145-3155), accumulated by every CalcChannelPreview; m_nWarnYccClipNum only restarts in Reset() (:130)
     uint32_t stats[2482]; unsigned warn_ycc_clip; bool hist_latched, clip_latched;
@@ -108,6 +109,14 @@ struct JsnoopBatch {
     hipEvent_t ev2[JSNOOP_NUM_STAGES + 1];                        // stage events of the second half (timed decodes)
     bool last_timed_split = false;
     bool last_used_parallel = false;                              // false: no table set of the batch fits the parallel path, the exact-mirror kernel decoded everything
+    // DC-only fast form (k_write_dc + k_dc_color): which form produced the results the batch holds now -- 0 nothing decoded, 1 generic, 2 fast.  After a
+    // form-2 decode the coefficient arena does NOT hold this decode's blocks: whoever reads dev.coef outside the decode calls ensure_generic() first.
+    int  last_form = 0;
+    bool force_generic = false;                                   // set around a re-decode in the generic form
+    bool private_no_log = false;                                  // the private batch of a single-image decoder without a log callback: its event arena stays unused by a clean decode
+    bool dc_fast_applies() const;                                 // the conditions of the fast form for the batch as uploaded
+    int  redecode_generic();                                      // the same batch once more through the Full-IDCT kernels, waited for (no fix-up)
+    int  ensure_generic();                                        // no-op unless last_form == 2: redecode_generic + the fix-up of sync()
     uint32_t* d_side_tmp = nullptr; size_t side_tmp_cap = 0;      // scratch of the side-output pass (one image at a time)
     uint8_t* pinned; size_t pinned_cap; uint64_t raw_bytes;
     uint8_t* d2h_land = nullptr;                                  // page-locked landing buffer of the read-back calls (32 MiB, on first use)

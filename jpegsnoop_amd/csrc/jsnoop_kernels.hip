@@ -1121,6 +1121,78 @@ __global__ void __launch_bounds__(256) k_status_reduce(const JsImage* __restrict
     }
 }
 
+// Back end of the DC-only fast form: cumulative DC -> DIB, no coefficient reads, no LDS tile.  In DC-only mode the reference never runs the IDCT
+// (:1818-1831) and every sample of a block is the block's cumulative DC ((short)((short)(0 * 8) + dc), :2517-2519): an 8 x 8 luma block has ONE colour.
+// Fast layouts only (js_fast_layout; eh, ev wave-uniform run-time values, so a launch may mix the four).  A lane owns a quad of four pixels of a
+// luma-block row: it reads the block's Y and its MCU's Cb / Cr from dccum (decode order: m * nb + j, j as blk_ch / blk_cv place the blocks for
+// k_idct_color), converts once and stores eight 16-byte quads, one per pixel row -- the 64 lanes of a wave cover 32 neighbouring luma blocks, every
+// store instruction 1 KiB of one DIB row (bottom-up).  Brightest pixel, sum of Y and the planes arena as k_idct_color leaves them.
+__global__ void __launch_bounds__(BK_THREADS) k_dc_color(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ wg_base, uint32_t nimg,
+                                                         const int16_t* __restrict__ dccum, uint8_t* __restrict__ dib, int16_t* __restrict__ planes,
+                                                         uint32_t* __restrict__ side, unsigned long long* __restrict__ wg_part)
+{
+    __shared__ unsigned long long s_bright[BK_WAVES]; __shared__ uint32_t s_sum[BK_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t lo = 0, hi = nimg;                                  // wg_base is an exclusive prefix, nimg+1 entries
+    const uint32_t bx0 = blockIdx.x + wg_base[0];
+    while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (wg_base[mid] <= bx0) lo = mid; else hi = mid; }
+    const JsImage& im = imgs[lo];
+    const uint32_t wg_in_img = bx0 - wg_base[lo], wgs_in_img = wg_base[lo + 1] - wg_base[lo];
+    const uint32_t eh = im.expand_h[2], ev = im.expand_v[2], nb = eh * ev + 2u;
+    const uint32_t img_x = im.img_x, img_y = im.img_y, nbx = img_x >> 3, nby = img_y >> 3, xmax = im.mcu_xmax;
+    // Decode order inside an MCU of a fast layout: the eh x ev luma blocks row by row (block (ch, cv) is number cv * eh + ch), then Cb, then Cr -- the order
+    // blk_comp / blk_ch / blk_cv of the descriptor spell out, which the host compares with this rule before it chooses the form (js_dc_fast_order).
+    const uint32_t jcb = eh * ev, jcr = jcb + 1u;
+    const int16_t* d = dccum + im.coef_off;
+    uint8_t* dibp = dib + im.dib_off;
+    const bool want_planes = im.want_planes != 0;
+    const uint32_t pw = im.blk_xmax * 8; const size_t psz = (size_t)pw * im.blk_ymax * 8;
+    int16_t* pb = planes + im.plane_off;
+    const uint32_t chunks = (nbx + 31u) >> 5, tasks = nby * chunks;      // a wave's task: 32 neighbouring luma blocks of one block row
+    uint64_t bright = 0; uint32_t sum_y = 0;
+    for (uint32_t t = wg_in_img * BK_WAVES + wave; t < tasks; t += wgs_in_img * BK_WAVES) {
+        const uint32_t by = t / chunks, bx = (t - by * chunks) * 32u + (lane >> 1);
+        if (bx >= nbx) continue;
+        const uint32_t m = (by >> (ev - 1u)) * xmax + (bx >> (eh - 1u));
+        const int16_t* dm = d + (size_t)m * nb;
+        const int y = dm[(by & (ev - 1u)) * eh + (bx & (eh - 1u))], cb = dm[jcb], cr = dm[jcr];
+        const int cy = clamp_s8(y >> 3);
+        const uint32_t px = bx * 8u + (lane & 1u) * 4u, py0 = by * 8u;
+        const uint32_t c = pack_bgr(ycc_core<true>((float)cy, chroma_r((float)clamp_s8(cr >> 3)), chroma_b((float)clamp_s8(cb >> 3))));
+        uint4 v; v.x = c; v.y = c; v.z = c; v.w = c;
+        uint8_t* top = dibp + ((size_t)(img_y - 1u - py0) * img_x + px) * 4u;      // the block's first pixel row has its highest address
+        #pragma unroll
+        for (uint32_t r = 0; r < 8; r++) *reinterpret_cast<uint4*>(top - (size_t)r * img_x * 4u) = v;
+        sum_y += 32u * (uint32_t)(cy + 128);                                       // nSumY += nFinalY (:4751) for the lane's 32 pixels
+        if (!(lane & 1u)) {                                                        // the block's earliest raster position is its top-left pixel
+            const uint64_t key = ((uint64_t)(uint32_t)(y + 32768) << 32) | (0xFFFFFFFFu - (py0 * img_x + px));
+            bright = key > bright ? key : bright;
+        }
+        if (want_planes) {
+            const uint32_t wy = (uint32_t)(uint16_t)y * 0x10001u, wcb = (uint32_t)(uint16_t)cb * 0x10001u, wcr = (uint32_t)(uint16_t)cr * 0x10001u;
+            #pragma unroll
+            for (uint32_t r = 0; r < 8; r++) {
+                const size_t pi = (size_t)(py0 + r) * pw + px;
+                *reinterpret_cast<uint2*>(pb + pi) = make_uint2(wy, wy); *reinterpret_cast<uint2*>(pb + psz + pi) = make_uint2(wcb, wcb); *reinterpret_cast<uint2*>(pb + 2 * psz + pi) = make_uint2(wcr, wcr);
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t ob = __shfl_down(bright, off); bright = ob > bright ? ob : bright;
+        sum_y += __shfl_down(sum_y, off);
+    }
+    if (lane == 0) { s_bright[wave] = bright; s_sum[wave] = sum_y; }
+    __syncthreads();
+    if (tid == 0) {                                              // one record or one pair of atomics per workgroup, as k_idct_color
+        for (uint32_t w = 1; w < BK_WAVES; w++) { bright = s_bright[w] > bright ? s_bright[w] : bright; sum_y += s_sum[w]; }
+        if (wg_part) { wg_part[2 * (size_t)bx0] = bright; wg_part[2 * (size_t)bx0 + 1] = sum_y; return; }
+        uint32_t* sd = side + im.side_off;
+        unsigned long long* bp = reinterpret_cast<unsigned long long*>(sd + 12);
+        if ((unsigned long long)bright > __atomic_load_n(bp, __ATOMIC_RELAXED)) atomicMax(bp, (unsigned long long)bright);
+        atomicAdd(sd + 15, sum_y);
+    }
+}
+
 // One block through the device IDCT (known-answer probe for jsnoop_idct_block): the production term loop, then the reference's * 0.25.
 __global__ void __launch_bounds__(64) k_idct_probe(const float* __restrict__ lut_t, const int16_t* __restrict__ coef64, float* __restrict__ out64)
 {
@@ -1402,6 +1474,15 @@ int js_launch_idct_color(hipStream_t st, const JsImage* imgs, const uint32_t* wg
     case 4: hipLaunchKernelGGL(k_idct_color<4>, dim3(total_wgs), dim3(BK_THREADS), lds, st, imgs, wg_base, nimg, tile_bytes, lut_t, coef, dccum, dib, planes, side, wg_part); break;
     default: hipLaunchKernelGGL(k_idct_color<0>, dim3(total_wgs), dim3(BK_THREADS), lds, st, imgs, wg_base, nimg, tile_bytes, lut_t, coef, dccum, dib, planes, side, wg_part); break;
     }
+    if (wg_part) hipLaunchKernelGGL(k_status_reduce, dim3(nimg), dim3(256), 0, st, imgs, wg_base, wg_part, side);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// DC-only fast form: every image of the launch has a fast layout and decode_ac == 0 (the host checks); the status reduction as above
+int js_launch_dc_color(hipStream_t st, const JsImage* imgs, const uint32_t* wg_base, uint32_t nimg, uint32_t total_wgs,
+                       const int16_t* dccum, uint8_t* dib, int16_t* planes, uint32_t* side, unsigned long long* wg_part)
+{
+    if (!total_wgs) return 0;
+    hipLaunchKernelGGL(k_dc_color, dim3(total_wgs), dim3(BK_THREADS), 0, st, imgs, wg_base, nimg, dccum, dib, planes, side, wg_part);
     if (wg_part) hipLaunchKernelGGL(k_status_reduce, dim3(nimg), dim3(256), 0, st, imgs, wg_base, wg_part, side);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -3324,6 +3405,173 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
     }
 }
 
+// WRITE pass of the DC-only fast form (every image of the launch has decode_ac == 0 and goes on to k_dc_color): the walk of k_write2 --
+// same entry states, same steps, same walk_slow at interval ends, same verification, flags, anomaly keys and restart marks, word for
+// word -- without anything that serves the coefficient arena: no lane-private block in LDS, no de-zigzag store, no flush.  What a block
+// leaves is its dequantised DC difference, queued eight per lane into dccum exactly as there.  LDS holds the decode tables only, so a
+// CU takes as many workgroups as its wave slots allow.  One lane per sub-sequence always (the middle states of the candidate chain are
+// an accelerator, not part of the result).
+template <int WL>
+__global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
+                                                         const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
+                                                         const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
+                                                         int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
+                                                         uint32_t tab_rows, uint32_t tab_lut2)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+    const uint32_t wg = blockIdx.x + sy_base[0];
+    const uint32_t img = find_image(sy_base, nimg, wg);
+    const JsImage& im = imgs[img];
+    if (!tables[im.tableset].lut_ok) return;
+    const uint32_t* sd = side + im.side_off;
+    const uint32_t total_bits = sd[10] * 8, nseg = min(sd[11], im.seg_cap - 1);
+    const uint32_t sub0 = (wg - sy_base[img]) * SY_THREADS, i = sub0 + threadIdx.x;
+    if (sub0 * SUB_BITS >= total_bits) return;
+    if (im.total_blocks >= (1u << 25)) { if (threadIdx.x == 0) { FLAG_OR(flags, img, F_SHORT); ANOM_MIN(flags, img, ANOM_KEY(0u, AK_MIRROR)); } return; }   // (as k_write2: the exact kernel's)
+    const JsTableSet& tset = tables[im.tableset];
+    SubTabs T; T.nb = im.blk_per_mcu; T.n1 = im.samp_h[1] * im.samp_v[1]; T.n2 = im.ncomp == 3 ? T.n1 + im.samp_h[2] * im.samp_v[2] : T.nb;
+    WriteTabs W; load_wtabs(W, s_dyn, tset, tab_rows, tab_lut2, im.ncomp, threadIdx.x, SY_THREADS);
+    __syncthreads();
+
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(ustr + im.ustr_off);
+    const uint32_t* st = seg_tab + im.seg_off;
+    int16_t* dbase = dccum + im.coef_off; uint8_t* rstf = mcu_rst + im.mcu_off;
+    const uint32_t nblocks = im.total_blocks, prec_shift = im.precision >= 8 ? ((im.precision - 8) & 31) : 0;
+    const bool in_data = i * SUB_BITS < total_bits;
+    const size_t g = im.subseq_off + i;
+    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = 0, c = 0, k = 0, seg_end = 0, blk = 0;
+    uint32_t res_p = 0, res_s = 0, res_n = 0;                // what this lane reports for verification
+    bool verify = false, check_n = false, active0 = false, skip0 = false;
+    const uint32_t own_end = min((i + 1) * SUB_BITS, total_bits);
+    Cursor cur; cur.words = words; cur.widx = 0; cur.poff = 0; cur.w0 = cur.w1 = cur.nxt = 0; cur.sh = 0; cur.p = 0;
+    if (in_data) {
+        const uint32_t p0 = i ? A.out_p[g - 1] : 0u, s0 = i ? A.out_s[g - 1] : 0u;
+        blk = A.base[g]; seg = ST_SEG(s0); c = ST_C(s0); k = ST_K(s0);
+        verify = true;
+        if (p0 != P_END && p0 >= own_end) { res_p = p0; res_s = s0; }                          // owns no symbol: passes through
+        else if (p0 == P_END || (p0 >= total_bits && seg + 1 >= nseg)) { res_p = P_END; res_s = 0; check_n = true; }
+        else if (blk >= nblocks) verify = false;                                                // everything owned lies past the last MCU
+        else { active0 = true; check_n = true; seg_end = st[seg + 1] * 8; skip0 = k != 0; cur_init<WL>(cur, words, p0); }
+    }
+    const uint32_t wb0 = W.wb0, wb1 = W.wb1, wb2 = W.wb2;       // per component: byte offset of its DC row | of its AC row << 16
+    const char* l1b = W.rows;
+    const uint32_t qd0 = W.qz[0] & 0xFFFFu, qd1 = W.qz[64] & 0xFFFFu, qd2 = W.qz[128] & 0xFFFFu;     // the three DC quantisers
+    uint32_t comp = comp_of(T, c), wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
+    uint64_t m_act = WBALLOT(active0), m_skip = WBALLOT(skip0), m_cap = 0ull;
+    uint32_t dcq0 = 0, dcq1 = 0, dcq2 = 0, dcq3 = 0, dccnt = 0, dclast = 0, dq0 = 0;      // the DC queue of k_write2
+    uint32_t rst_blk = 0xFFFFFFFFu;
+    for (;;) {
+        // ---- end of the owned range
+        const uint64_t m_end = WBALLOT(cur.p >= own_end) & m_act;
+        if (m_end) {
+            if (IBAL(m_end & ~m_cap)) { res_p = cur.p; res_s = ST_MAKE(seg, c, k); res_n = nblk; }
+            m_cap |= m_end;
+            m_act &= ~(m_end & (WBALLOT(k == 0) | m_skip));
+        }
+        if (!m_act) break;
+        // ---- table entry
+        const uint32_t win = cur_peek(cur);
+        const uint32_t widx = win >> (32 - JS_L1_BITS);
+        const uint64_t m_dc = WBALLOT(k == 0);
+        const uint32_t e_dc = (uint32_t)(int32_t)*reinterpret_cast<const int16_t*>(l1b + ((wb & 0xFFFFu) + (widx << 1)));
+        const uint32_t e_ac = *reinterpret_cast<const uint32_t*>(l1b + ((wb >> 16) + (widx << 2)));
+        uint32_t e = IBAL(m_dc) ? e_dc : e_ac;
+        uint32_t len = e & 15u, size = (e >> 4) & 15u, run = (e >> 8) & 15u;
+        const uint64_t m_esc = WBALLOT((int32_t)e < 0) & m_act;
+        if (m_esc) {
+            if (IBAL(m_esc)) {
+                const uint32_t nbx = (e >> 12) & 7u;
+                const uint32_t e2 = W.lut2[(e & 0xFFFu) + __builtin_amdgcn_ubfe(win, 32u - JS_L1_BITS - nbx, nbx)];
+                const bool nocode = e == 0xC0000000u;
+                len = nocode ? 0u : (e2 >> 8) & 31u; run = nocode ? 0u : (e2 >> 4) & 15u; size = nocode ? 0u : e2 & 15u;
+                e = 0;
+            }
+        }
+        uint32_t tot = len + size;
+        uint32_t k2 = k + run + 1u;
+        const uint32_t len2 = (e >> 12) & 15u, size2 = (e >> 16) & 15u, run2 = (e >> 20) & 15u, tot2 = len2 + size2, k3 = k2 + run2 + 1u;
+        const uint32_t p1 = cur.p + tot, p2 = p1 + tot2;
+        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & m_act;
+        // ---- anything out of the ordinary, behind one vote
+        uint64_t m_norm = m_act, m_bad = 0ull;
+        const uint64_t m_abn = (WBALLOT(len == 0u) | WBALLOT(p1 > seg_end) | WBALLOT(k2 > 64u)) & m_act;
+        if (m_abn) {
+            const uint64_t m_slow = (WBALLOT(len == 0u) | WBALLOT(cur.p + len > seg_end)) & m_act;
+            bool over = false, bad = false;
+            if (IBAL(m_slow)) {
+                const bool notcap = !IBAL(m_cap);
+                const uint32_t seg_was = seg;
+                const int ws = walk_slow<true, WL>(im, words, st, nseg, cur, len, seg, seg_end, c, k, blk, notcap, rstf, fl, an);
+                rst_blk = seg != seg_was ? blk : rst_blk;
+                if (ws == WS_OVER && notcap) { res_p = P_END; res_s = 0; res_n = nblk; }
+                over = ws == WS_OVER; bad = ws == WS_BAD_CODE;
+                comp = comp_of(T, c); wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
+                tot = 0; size = 0; k2 = k;
+            } else if (IBAL(m_act)) {
+                if (blk < nblocks) {
+                    if (p1 > seg_end) { fl |= F_OVERRUN; an = min(an, ANOM_KEY(blk, seg + 1u < nseg ? AK_DEAD + (IBAL(m_dc) ? 0u : 1u) + (rst_blk == blk ? 2u : 0u) + (IBAL(m_skip) ? 4u : 0u) : AK_MIRROR)); }
+                    if (k2 > 64u) fl |= F_COEF_OVERFLOW;
+                }
+            }
+            const uint64_t m_over = WBALLOT(over);
+            m_bad = WBALLOT(bad) & m_act;
+            m_cap |= m_over; m_act &= ~m_over;
+            m_norm &= ~m_slow; m_two &= ~m_slow;
+        }
+        // ---- the DC difference: EXTEND, precision divide, dequantise (AC values are parsed, not formed)
+        int32_t val = extend_bits(win, len, size);
+        if (prec_shift) val /= (int32_t)(1u << prec_shift);
+        const uint32_t qd = comp == 0 ? qd0 : (comp == 1 ? qd1 : qd2);
+        dq0 = IBAL(m_dc & m_norm) ? (uint32_t)((int32_t)(int16_t)val * (int32_t)qd) : dq0;
+        if (m_bad) { if (IBAL(m_bad & m_dc)) dq0 = 0u; }          // a code that matches nothing in front of the DC value: the block keeps a zero difference
+        // ---- advance
+        const bool two = IBAL(m_two);
+        { const uint32_t adv = tot + (two ? tot2 : 0u); cur.sh -= (int32_t)adv; cur.p += adv; }
+        if (IBAL(WBALLOT(cur.sh < 0) & m_act)) {
+            cur.sh += 32; cur.w0 = cur.w1; cur.w1 = bswap32(cur.nxt);
+            cur.nxt = cur_fetch<WL>(cur);
+        }
+        const uint32_t kn = two ? k3 : k2;
+        const uint64_t m_eob = (m_two & WBALLOT((run2 | size2) == 0u)) | (~m_two & WBALLOT((run | size) == 0u));
+        const uint64_t m_done = (m_norm & ~m_dc & (m_eob | WBALLOT(kn >= 64u))) | m_bad;
+        k = IBAL(m_done) ? 0u : kn;
+        if (m_done) {
+            const uint64_t m_flush = m_done & ~m_skip & WBALLOT(blk < nblocks);
+            const uint32_t fblk = blk;
+            if (IBAL(m_done)) {
+                c = c + 1 == T.nb ? 0u : c + 1; comp = comp_of(T, c); wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
+                nblk += IBAL(m_cap) ? 0u : 1u;
+                blk++;
+            }
+            m_skip &= ~m_done;
+            if (m_flush) {
+                if (IBAL(m_flush)) {
+                    dcq0 = __builtin_amdgcn_alignbit(dcq1, dcq0, 16u); dcq1 = __builtin_amdgcn_alignbit(dcq2, dcq1, 16u); dcq2 = __builtin_amdgcn_alignbit(dcq3, dcq2, 16u);
+                    dcq3 = (dcq3 >> 16) | (dq0 << 16); dccnt++; dclast = fblk;
+                }
+                if (WBALLOT(dccnt >= 8u)) {
+                    if (dccnt >= 8u) {
+                        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+                        u32x4_t t; t.x = dcq0; t.y = dcq1; t.z = dcq2; t.w = dcq3;
+                        *reinterpret_cast<u32x4_t*>(dbase + (dclast - 7u)) = t;
+                        dccnt = 0;
+                    }
+                }
+            }
+        }
+    }
+    #pragma unroll
+    for (uint32_t h = 0; h < 8; h++) {                           // what is left of the queue: the newest dccnt values sit in the top halves
+        const uint32_t q = h < 2 ? dcq0 : (h < 4 ? dcq1 : (h < 6 ? dcq2 : dcq3));
+        if (h + dccnt >= 8u) dbase[dclast - 7u + h] = (int16_t)((h & 1u) ? q >> 16 : q);
+    }
+    if (verify) {
+        if (check_n && !IBAL(m_cap) && res_p != P_END) { res_p = cur.p; res_s = cur.p == P_END ? 0u : ST_MAKE(seg, c, k); res_n = nblk; }
+        if (res_p != A.out_p[g] || res_s != A.out_s[g] || (check_n && res_n != A.nblk[g])) fl |= F_NOSYNC;
+    }
+    if (fl) { FLAG_OR(flags, img, fl); if (an != 0xFFFFFFFFu) ANOM_MIN(flags, img, an); }
+}
+
 // One workgroup (1024 lanes) per image: DC differences (in dccum, decode order) -> cumulative DC per block.
 // int16 wrapping sums per component (m_nDcLum += ..., :3280/:3355/:3386), reset at every MCU the write pass marked as
 // the first of a restart interval (DecodeRestartDcState :2693).  One lane per MCU, 1024 MCUs per step: the lanes of a
@@ -3585,6 +3833,16 @@ void js_launch_write(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut
                        sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
     else hipLaunchKernelGGL((k_write<5, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
                        sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
+}
+// the write pass of the DC-only fast form (k_write_dc): no coefficient arena, one lane per sub-sequence
+void js_launch_write_dc(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* sy_base, uint32_t nimg, uint32_t total_wgs, const JsTableSet* tables,
+                        const uint8_t* ustr, const uint32_t* seg_tab, uint32_t* side, uint32_t* sub, uint64_t nsub, int16_t* dccum, uint8_t* mcu_rst, uint32_t* flags)
+{
+    if (!total_wgs) return;
+#define JS_WRITE_DC(W) hipLaunchKernelGGL((k_write_dc<W>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side, \
+                                          sub_arrays(sub, nsub), dccum, mcu_rst, flags, tab_rows, tab_lut2)
+    if (wl == 4) JS_WRITE_DC(4); else if (wl == 6) JS_WRITE_DC(6); else if (wl == 7) JS_WRITE_DC(7); else if (wl == 8) JS_WRITE_DC(8); else JS_WRITE_DC(5);
+#undef JS_WRITE_DC
 }
 // =====================================================================================
 //  Side outputs of an image the parallel path decoded, without the sequential kernel:

@@ -53,6 +53,11 @@ void js_launch_write(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut
                      int16_t* coef, int16_t* dccum, uint8_t* mcu_rst, uint32_t* flags,
                      uint32_t* cand_half /* null, or the candidate arena of a job that was synchronised by candidates: two lanes per sub-sequence (64-byte pieces only) */, bool v1,
                      uint32_t* rec_pos = nullptr /* 64-byte pieces, !v1: the pass records MCU-top bit positions here and the code-length histogram in the side block (the side walk's outputs) */);
+// DC-only fast form (every image decode_ac == 0, fast layout): the write pass without the coefficient arena, and the back end straight from cumulative DC to DIB
+void js_launch_write_dc(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* sy_base, uint32_t nimg, uint32_t total_wgs, const JsTableSet* tables,
+                        const uint8_t* ustr, const uint32_t* seg_tab, uint32_t* side, uint32_t* sub, uint64_t nsub, int16_t* dccum, uint8_t* mcu_rst, uint32_t* flags);
+int  js_launch_dc_color(hipStream_t st, const JsImage* imgs, const uint32_t* wg_base, uint32_t nimg, uint32_t total_wgs,
+                        const int16_t* dccum, uint8_t* dib, int16_t* planes, uint32_t* side, unsigned long long* wg_part);
 // side-output pass over one image the parallel path decoded (MCU file map, block-DC maps, code-length histogram, status words)
 void js_launch_side_pass(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* us_base, const uint32_t* sy_base, uint32_t nimg,
                          uint32_t img, uint32_t us_wg0, uint32_t us_wgs, uint32_t sy_wg0, uint32_t sy_wgs, const JsTableSet* tables, const uint8_t* raw,

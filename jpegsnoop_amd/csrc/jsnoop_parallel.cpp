@@ -327,6 +327,10 @@ int js_parallel_entropy_part(JsnoopBatch* b, hipStream_t st, uint32_t i0, uint32
     roctxRangePushA("jsnoop:block scan + coefficient write + DC scan");
     js_launch_block_scan(st, b->sub_wl, imgs, n, b->dev.tables, sub, b->total_subseq, b->dev.side, flags);
     if (evs) HIP_TRY(hipEventRecord(evs[4], st));
+    if (b->last_form == 2)                                         // DC-only fast form: the same walk, nothing for the coefficient arena (k_write_dc)
+        js_launch_write_dc(st, b->sub_wl, b->tab_rows_w, b->tab_lut2, imgs, sy_base, n, sy_wgs, b->dev.tables, b->dev.ustr, b->dev.seg, b->dev.side, sub, b->total_subseq,
+                           b->dev.dccum, b->dev.mcu_rst, flags);
+    else
     js_launch_write(st, b->sub_wl, b->tab_rows_w, b->tab_lut2, imgs, sy_base, n, sy_wgs, b->dev.tables, b->dev.ustr, b->dev.seg, b->dev.side, sub, b->total_subseq,
                     b->dev.coef, b->dev.dccum, b->dev.mcu_rst, flags, b->cand_half ? b->dev.cand : nullptr, (b->tune.cross_checks & JSNOOP_XC_WRITE_V1) != 0, b->rec_pos);
     if (evs) HIP_TRY(hipEventRecord(evs[5], st));
@@ -349,6 +353,7 @@ int JsnoopBatch::run_exact(const std::vector<uint32_t>& which)
 {
     if (which.empty()) return 0;
     HIP_TRY(hipSetDevice(device));
+    if (ensure_generic()) return -1;
     for (uint32_t i : which) {
         const JsImage& im = imgs[i];
         HIP_TRY(hipMemsetAsync(dev.coef + im.coef_off * 64, 0, (size_t)im.total_blocks * 128, stream));
@@ -368,6 +373,7 @@ int JsnoopBatch::redo_back_end(const std::vector<uint32_t>& which)
 {
     if (which.empty()) return 0;
     HIP_TRY(hipSetDevice(device));
+    if (ensure_generic()) return -1;                              // (the colour kernel of a repair reads the coefficient arena)
     const uint32_t n = (uint32_t)imgs.size();
     if (which.size() * 8 >= n && which.size() > 1) {
         // (words 12-13: brightest-pixel key, 15: sum of Y -- the back end's reductions; word 14, the block count of k_block_scan, stays)
@@ -388,7 +394,8 @@ static int js_parallel_resume(JsnoopBatch* b, int extra_launches)
 {
     const uint32_t n = (uint32_t)b->imgs.size();
     uint32_t* sub = (uint32_t*)b->dev.sub;
-    HIP_TRY(hipMemsetAsync(b->dev.coef, 0, b->total_blocks * 128, b->stream));
+    const bool dc_fast = b->last_form == 2;                       // (DC-only fast form: the same repair with its own write pass and back end; the coefficient arena is not its business)
+    if (!dc_fast) HIP_TRY(hipMemsetAsync(b->dev.coef, 0, b->total_blocks * 128, b->stream));
     HIP_TRY(hipMemsetAsync(b->dev.dccum, 0, b->total_blocks * 2, b->stream));
     HIP_TRY(hipMemsetAsync(b->dev.mcu_rst, 0, b->mcu_bytes, b->stream));
     if (js_clear_flags(b)) return -1;
@@ -396,6 +403,10 @@ static int js_parallel_resume(JsnoopBatch* b, int extra_launches)
     for (int l = 0; l < extra_launches; l++)      // the first launch checks every link (a candidate chain may have left open ones anywhere), the others carry changes across workgroup boundaries
         js_launch_sync(b->stream, b->sub_wl, b->tab_rows, b->tab_lut2, b->dev.imgs, b->dev.sy_base + (n + 1), n, b->sn_wgs, b->dev.tables, b->dev.ustr, b->dev.seg, b->dev.side, sub, b->total_subseq, l == 0 ? 2 : 0);
     js_launch_block_scan(b->stream, b->sub_wl, b->dev.imgs, n, b->dev.tables, sub, b->total_subseq, b->dev.side, b->dev.flags);
+    if (dc_fast)
+        js_launch_write_dc(b->stream, b->sub_wl, b->tab_rows_w, b->tab_lut2, b->dev.imgs, b->dev.sy_base, n, b->sy_wgs, b->dev.tables, b->dev.ustr, b->dev.seg, b->dev.side, sub, b->total_subseq,
+                           b->dev.dccum, b->dev.mcu_rst, b->dev.flags);
+    else
     js_launch_write(b->stream, b->sub_wl, b->tab_rows_w, b->tab_lut2, b->dev.imgs, b->dev.sy_base, n, b->sy_wgs, b->dev.tables, b->dev.ustr, b->dev.seg, b->dev.side, sub, b->total_subseq,
                     b->dev.coef, b->dev.dccum, b->dev.mcu_rst, b->dev.flags, nullptr, (b->tune.cross_checks & JSNOOP_XC_WRITE_V1) != 0);      // (the middle states are the candidate chain's: one lane per sub-sequence here)
     js_launch_dc_scan(b->stream, b->dev.imgs, n, b->dev.tables, b->dev.dccum, b->dev.mcu_rst, b->dev.dc_parts);
@@ -449,12 +460,28 @@ int js_parallel_fixup(JsnoopBatch* b)
     // (a side pass launched behind the decode saw what the decode left: any flag -- a chain that needed more rounds included -- makes it stale)
     for (uint32_t i = 0; i < n && i < b->side_pre.size(); i++) if (b->host_flags[i]) b->side_pre[i] = 0;
     // An unconverged chain is not a malformed stream: give it more synchronisation rounds first.
-    for (int attempt = 0, extra = 4; attempt < 4; attempt++, extra *= 4) {
-        bool nosync = false;
-        for (uint32_t i = 0; i < n; i++) nosync = nosync || (b->host_flags[i] & JSNOOP_FLAG_NOSYNC);
-        if (!nosync) break;
-        if (js_parallel_resume(b, extra)) return -1;
+    auto more_rounds = [&]() -> int {
+        for (int attempt = 0, extra = 4; attempt < 4; attempt++, extra *= 4) {
+            bool nosync = false;
+            for (uint32_t i = 0; i < n; i++) nosync = nosync || (b->host_flags[i] & JSNOOP_FLAG_NOSYNC);
+            if (!nosync) break;
+            if (js_parallel_resume(b, extra)) return -1;
+        }
+        return 0;
+    };
+    // A DC-only fast-form decode vouches for clean images only.  A chain short of its fixed point is no damage: it gets its rounds in the fast form
+    // (js_parallel_resume follows last_form).  Any other flag or an anomaly anywhere -- or a chain that stays open -- and the batch is decoded again in
+    // the generic form: whatever a damaged file needs below (tail take-over, second attempts, the mirror) then finds the arenas it has always found.
+    if (b->last_form == 2) {
+        auto flagged = [&]() { bool f = false; for (uint32_t i = 0; i < n; i++) f = f || b->host_flags[i] || b->host_anom[i] != 0xFFFFFFFFu; return f; };
+        if (more_rounds()) return -1;                             // (walks from entry states that were not the real ones raise other flags along with NOSYNC: the repair clears them all)
+        if (flagged()) {
+            if (b->tune.debug & JSNOOP_DBG_TAIL) for (uint32_t i = 0; i < n; i++) if (b->host_flags[i] || b->host_anom[i] != 0xFFFFFFFFu)
+                fprintf(stderr, "[tail] image %u flags 0x%04x first anomalous block %u: the DC-only fast form hands the batch to the generic form\n", i, b->host_flags[i], b->host_anom[i]);
+            if (b->redecode_generic() || js_read_flags(b)) return -1;
+        }
     }
+    if (more_rounds()) return -1;
     // What the flags mean for the PIXELS: a run past the 64th coefficient (JSNOOP_FLAG_COEF_OVERFLOW) ends the block without a store in the
     // reference (:1723-1735: "ncoef > 64 -> done", the value bits are consumed) exactly as in the parallel walks -- coefficients, planes
     // and DIB of such an image are already the reference's; what the flag stands for is bookkeeping (scan_bad, the warning counter, two

@@ -120,6 +120,17 @@ static inline bool js_fast_layout(const JsImage& im)
            im.samp_h[2] == 1 && im.samp_v[2] == 1 && im.samp_h[3] == 1 && im.samp_v[3] == 1 && im.expand_h[3] == eh && im.expand_v[3] == ev &&
            eh >= 1 && eh <= 2 && ev >= 1 && ev <= 2;
 }
+// ... whose blocks come in the order k_dc_color computes with: luma block (ch, cv) is number cv * eh + ch of the MCU, Cb and Cr follow
+static inline bool js_dc_fast_order(const JsImage& im)
+{
+    const uint32_t eh = im.expand_h[2], ev = im.expand_v[2];
+    if (!js_fast_layout(im) || im.blk_per_mcu != eh * ev + 2u) return false;
+    for (uint32_t cv = 0; cv < ev; cv++) for (uint32_t ch = 0; ch < eh; ch++) {
+        const uint32_t j = cv * eh + ch;
+        if (im.blk_comp[j] != 1 || im.blk_ch[j] != ch || im.blk_cv[j] != cv) return false;
+    }
+    return im.blk_comp[eh * ev] == 2 && im.blk_comp[eh * ev + 1u] == 3;
+}
 // bytes of the back end's per-wave LDS tile for this image: Y plane + two bare chroma blocks (fast layouts), else three replicated planes
 static inline uint32_t js_tile_bytes(const JsImage& im)
 {

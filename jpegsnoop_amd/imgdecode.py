@@ -139,6 +139,9 @@ class CimgDecode:
     def LastPath(self): return self._lib.jsnoop_last_path(self._h)
     def LastFlags(self): return self._lib.jsnoop_last_flags(self._h)
     def LastSideMode(self): return self._lib.jsnoop_last_side_mode(self._h)
+    def last_form(self) -> int:
+        """Which form produced the results held now: 0 nothing decoded, 1 Full-IDCT kernels, 2 DC-only fast form (jsnoop_last_form)."""
+        return int(self._lib.jsnoop_last_form(self._h))
 
 
 class JpegBatch:
@@ -193,6 +196,9 @@ class JpegBatch:
     def upload(self): self._chk(self._lib.jsnoop_batch_upload(self._h), "batch_upload")
     def decode(self): self._chk(self._lib.jsnoop_batch_decode(self._h), "batch_decode")
     def sync(self): self._chk(self._lib.jsnoop_batch_sync(self._h), "batch_sync")
+    def last_form(self) -> int:
+        """Which form produced the results the batch holds now: 0 nothing decoded, 1 Full-IDCT kernels, 2 DC-only fast form (jsnoop_batch_last_form)."""
+        return int(self._lib.jsnoop_batch_last_form(self._h))
 
     def decode_timed(self, reps=1):
         st = (C.c_double * capi.NUM_STAGES)()
