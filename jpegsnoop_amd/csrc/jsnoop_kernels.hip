@@ -2104,6 +2104,10 @@ template <int WL> __device__ __forceinline__ void cur_skip(Cursor& c, uint32_t n
     c.sh -= (int32_t)n; c.p += n;
     if (c.sh < 0) { c.sh += 32; c.w0 = c.w1; c.w1 = bswap32(c.nxt); c.nxt = cur_fetch<WL>(c); }
 }
+// What one step of a walker may consume: cur_peek holds 32 valid bits of the stream, and one update of `sh` (in [0, 31] before it, one
+// refill of w0 / w1 behind it) covers an advance of 32 at most.  The pair entries of the tables never describe more than 24 bits; the
+// second symbol the write pass looks up by itself is bounded by this.
+#define JS_STEP_BITS 32u
 
 // state word: [31:12] interval index (up to 2^20 - 1 restart intervals), [11:6] block-in-MCU (< 48), [5:0] next coefficient index (0 = DC)
 #define ST_SEG(s) ((s) >> 12)
@@ -3261,16 +3265,24 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
                 const uint32_t e2 = W.lut2[(e & 0xFFFu) + __builtin_amdgcn_ubfe(win, 32u - JS_L1_BITS - nbx, nbx)];
                 const bool nocode = e == 0xC0000000u;            // (AC rows; a DC row says 0, which is "length 0" already)
                 len = nocode ? 0u : (e2 >> 8) & 31u; run = nocode ? 0u : (e2 >> 4) & 15u; size = nocode ? 0u : e2 & 15u;
-                e = 0;                                           // a single symbol
+                e = 1u << 24;                                    // a single symbol, and none is looked up behind it
             }
         }
         uint32_t tot = len + size;
         uint32_t k2 = k + run + 1u;                              // coefficient index behind this symbol (DC: k = 0, run = 0)
+        // ---- the symbol behind it, from a table read of its own: an entry that shows no second symbol (its code did not fit the
+        //      JS_L1_BITS window behind the first symbol's code AND value bits; DC rows never show one) takes the AC entry at the bits
+        //      that follow `tot` -- same row, same form, of which only the first symbol counts.  Not behind an escape, not behind an
+        //      EOB (the next symbol is another block's DC), not when that entry is an escape itself or no code: the step stays single.
+        //      (No code in front, len == 0: the lane is in m_slow, which clears m_two.)
+        const uint32_t win2 = win << tot;                        // (tot <= 31: a code of 16 bits at most, 15 value bits)
+        const uint32_t e_b = *reinterpret_cast<const uint32_t*>(l1b + ((wb >> 16) + ((win2 >> (32 - JS_L1_BITS)) << 2)));
+        if ((e >> 12) == 0u && (int32_t)e_b >= 0 && (IBAL(m_dc) || (e & 0xFF0u) != 0u)) e |= (e_b & 0xFFFu) << 12;
         // the AC symbol behind it goes along when the first one does not end the lane's own range, and nothing out of the ordinary can
         // happen on the way (interval end, coefficient overflow); an entry without a visible second symbol has zero bits there
         const uint32_t len2 = (e >> 12) & 15u, size2 = (e >> 16) & 15u, run2 = (e >> 20) & 15u, tot2 = len2 + size2, k3 = k2 + run2 + 1u;
         const uint32_t p1 = cur.p + tot, p2 = p1 + tot2;
-        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & m_act;
+        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & WBALLOT(tot + tot2 <= JS_STEP_BITS) & m_act;
         // ---- anything out of the ordinary sits behind one vote: no code, the end of the interval inside the code or its value
         //      bits, a run past the 64th coefficient
         uint64_t m_norm = m_act, m_nost = 0ull, m_bad = 0ull;      // m_bad: a code that matches nothing ended the lane's block (walk_slow)
@@ -3311,7 +3323,7 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
             if (IBAL(m_bad & ~m_cap) && blk < nblocks) atomicAdd(&s_histo[(IBAL(m_dc) ? hd : 4u + ha) * 17u + 1u], 1u);     // (one bit "used", :1178-1186)
         }
         // ---- value bits: EXTEND (HuffmanDc2Signed :859), precision divide (:1234-1238), dequantise (:2278), de-zigzag
-        int32_t val = extend_bits(win, len, size), val2 = extend_bits(win, tot + len2, size2);
+        int32_t val = extend_bits(win, len, size), val2 = extend_bits(win2, len2, size2);
         if (prec_shift) { val /= (int32_t)(1u << prec_shift); val2 /= (int32_t)(1u << prec_shift); }
         const char* qrow = qzb + comp * 256u;
         const uint32_t qz = *reinterpret_cast<const uint32_t*>(qrow + (((k2 - 1u) & 63u) << 2));           // DC: 0, AC: k + run
@@ -3336,7 +3348,7 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
         }
         const uint32_t kn = two ? k3 : k2;
         const uint64_t m_eob = (m_two & WBALLOT((run2 | size2) == 0u)) | (~m_two & WBALLOT((run | size) == 0u));
-        const uint64_t m_done = (m_norm & ~m_dc & (m_eob | WBALLOT(kn >= 64u))) | m_bad;
+        const uint64_t m_done = (m_norm & (~m_dc | m_two) & (m_eob | WBALLOT(kn >= 64u))) | m_bad;   // (a DC symbol ends no block; the AC symbol that went along with it may)
         k = IBAL(m_done) ? 0u : kn;
         if (m_done) {
             const uint64_t m_flush = m_done & ~m_skip & WBALLOT(blk < nblocks);
@@ -3484,14 +3496,18 @@ __global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restri
                 const uint32_t e2 = W.lut2[(e & 0xFFFu) + __builtin_amdgcn_ubfe(win, 32u - JS_L1_BITS - nbx, nbx)];
                 const bool nocode = e == 0xC0000000u;
                 len = nocode ? 0u : (e2 >> 8) & 31u; run = nocode ? 0u : (e2 >> 4) & 15u; size = nocode ? 0u : e2 & 15u;
-                e = 0;
+                e = 1u << 24;
             }
         }
         uint32_t tot = len + size;
         uint32_t k2 = k + run + 1u;
+        // ---- the symbol behind it, from a table read of its own (as k_write2)
+        const uint32_t win2 = win << tot;
+        const uint32_t e_b = *reinterpret_cast<const uint32_t*>(l1b + ((wb >> 16) + ((win2 >> (32 - JS_L1_BITS)) << 2)));
+        if ((e >> 12) == 0u && (int32_t)e_b >= 0 && (IBAL(m_dc) || (e & 0xFF0u) != 0u)) e |= (e_b & 0xFFFu) << 12;
         const uint32_t len2 = (e >> 12) & 15u, size2 = (e >> 16) & 15u, run2 = (e >> 20) & 15u, tot2 = len2 + size2, k3 = k2 + run2 + 1u;
         const uint32_t p1 = cur.p + tot, p2 = p1 + tot2;
-        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & m_act;
+        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & WBALLOT(tot + tot2 <= JS_STEP_BITS) & m_act;
         // ---- anything out of the ordinary, behind one vote
         uint64_t m_norm = m_act, m_bad = 0ull;
         const uint64_t m_abn = (WBALLOT(len == 0u) | WBALLOT(p1 > seg_end) | WBALLOT(k2 > 64u)) & m_act;
@@ -3533,7 +3549,7 @@ __global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restri
         }
         const uint32_t kn = two ? k3 : k2;
         const uint64_t m_eob = (m_two & WBALLOT((run2 | size2) == 0u)) | (~m_two & WBALLOT((run | size) == 0u));
-        const uint64_t m_done = (m_norm & ~m_dc & (m_eob | WBALLOT(kn >= 64u))) | m_bad;
+        const uint64_t m_done = (m_norm & (~m_dc | m_two) & (m_eob | WBALLOT(kn >= 64u))) | m_bad;   // (a DC symbol ends no block; the AC symbol that went along with it may)
         k = IBAL(m_done) ? 0u : kn;
         if (m_done) {
             const uint64_t m_flush = m_done & ~m_skip & WBALLOT(blk < nblocks);

@@ -4,6 +4,8 @@
 #   runs of the SAME library is measured next to the difference between the two.  Per run: the one-stream stage times (bench.py --full --no-extras),
 #   the default two-stream headline (bench.py) and the rocprofv3 per-kernel averages of the profiled one-stream form.  Every GPU step has a time limit
 #   of its own and the first one that fails ends the call.  Results in the output directory, the table on stdout.
+#   AB_KERNEL (default "k_idct_color<1>") and AB_STAGE (default idct_color) choose the kernel and the stage of the table,
+#   e.g. AB_KERNEL="k_write2<7" AB_STAGE=write for the write pass (profiles/r09_second_symbol.txt).
 set -o pipefail
 mkdir -p "$1" || exit 1
 OUT=$(realpath "$1"); VAR=$(realpath "$2"); PAIRS=${3:-3}
@@ -24,16 +26,16 @@ one() {   # name, library, run number
 for i in $(seq 1 "$PAIRS"); do
   one tree "$TREE" "$i" && one variant "$VAR" "$i" || { echo "run $i failed: stopping (see $OUT/*.err)"; exit 1; }
 done
-python - "$OUT" "$PAIRS" <<'PY'
+python - "$OUT" "$PAIRS" "${AB_KERNEL:-k_idct_color<1>}" "${AB_STAGE:-idct_color}" <<'PY'
 import csv, json, sys
-out, pairs = sys.argv[1], int(sys.argv[2])
+out, pairs, kernel, stage = sys.argv[1], int(sys.argv[2]), sys.argv[3], sys.argv[4]
 def row(name, i):
     f = json.load(open("%s/full_%s_%d.json" % (out, name, i))); d = json.load(open("%s/default_%s_%d.json" % (out, name, i)))
-    k = [r for r in csv.reader(open("%s/kernel_stats_%s_%d.csv" % (out, name, i))) if "k_idct_color<1>" in r[0]][0]      # Name, Calls, TotalDurationNs, AverageNs, ...
-    return dict(stage=f["roofline"]["stages_ms"]["idct_color"], one_stream=f["one_stream"]["ms_per_step"], step=d["ms_per_step"],
+    k = [r for r in csv.reader(open("%s/kernel_stats_%s_%d.csv" % (out, name, i))) if kernel in r[0]][0]      # Name, Calls, TotalDurationNs, AverageNs, ...
+    return dict(stage=f["roofline"]["stages_ms"][stage], one_stream=f["one_stream"]["ms_per_step"], step=d["ms_per_step"],
                 exact=bool(f["bit_exact"]) and bool(d["bit_exact"]), kernel=float(k[3]) / 1e6)
 rows = {(n, i): row(n, i) for n in ("tree", "variant") for i in range(1, pairs + 1)}
-print("%-10s %10s %12s %12s %12s  %s" % ("run", "idct_color", "one-stream", "ms_per_step", "kernel avg", "bit-exact"))
+print("%-10s %10s %12s %12s %12s  %s" % ("run", stage, "one-stream", "ms_per_step", "kernel avg", "bit-exact"))
 for i in range(1, pairs + 1):
     for n in ("tree", "variant"):
         r = rows[n, i]
