@@ -83,14 +83,17 @@ def coefs_of(tokens, pred):
     return out if k == 64 else None
 
 
-def write(frame, tabs, comp_ids, blocks, dri=0):
+def write(frame, tabs, comp_ids, blocks, dri=0, rst_before=()):
     """frame: prog_codec.Frame; tabs: {(class, id): (counts, symbols)} (class 0 DC, 1 AC; ids 0..3); comp_ids: per component
-    (DC id, AC id); blocks: one entry per block in decode order -- a sequence of 64 numbers (coefficients) or a list of tokens."""
+    (DC id, AC id); blocks: one entry per block in decode order -- a sequence of 64 numbers (coefficients) or a list of tokens.
+    rst_before: block indices (decode order) in front of which the interval is closed and the next RSTn written besides those the
+    restart interval asks for -- a marker inside an MCU, or a second one on an MCU boundary that already has one."""
     bpm = frame.mcu_blocks(); units = frame.mcu_x * frame.mcu_y
     assert len(blocks) == units * len(bpm), (len(blocks), units, len(bpm))
     codes = {key: P._codes(t) for key, t in tabs.items()}
     census = []; coefs = []; iv_ends = []; body = bytearray(); raw = bytearray()
-    w = P._Bits(); nb = 0; base = 0; iv = 0; pred = [0] * frame.ncomp
+    w = P._Bits(); nb = 0; base = 0; iv = 0; pred = [0] * frame.ncomp; extra = frozenset(int(b) for b in rst_before)
+    assert all(0 < b < len(blocks) for b in extra), "a marker lies between two blocks"
 
     def close_interval(marker):
         nonlocal w, nb, base, iv
@@ -102,9 +105,11 @@ def write(frame, tabs, comp_ids, blocks, dri=0):
 
     for u in range(units):
         if dri and u and u % dri == 0:
-            close_interval(u // dri - 1); pred = [0] * frame.ncomp
+            close_interval(iv); pred = [0] * frame.ncomp             # (RSTn counts the markers written: iv == u // dri - 1 without rst_before)
         for j, (c, _y, _x) in enumerate(bpm):
             blk = blocks[u * len(bpm) + j]; bi = u * len(bpm) + j
+            if bi in extra:
+                close_interval(iv); pred = [0] * frame.ncomp
             is_tokens = len(blk) != 64 or isinstance(blk[0], tuple)
             T = list(blk) if is_tokens else tokens_of(blk, pred[c])
             want = coefs_of(T, pred[c])
@@ -131,7 +136,7 @@ def write(frame, tabs, comp_ids, blocks, dri=0):
         p += bytes([c + 1, comp_ids[c][0] << 4 | comp_ids[c][1]])
     out += P._seg(0xDA, p + bytes([0, 63, 0])) + body + b"\xFF\xD9"
     return Stream(file=bytes(out), raw=bytes(raw), census=census, bits=base, iv_ends=iv_ends, coefs=coefs, frame=frame, tabs=tabs, comp_ids=comp_ids,
-                  dri=dri)
+                  dri=dri, rst_before=sorted(extra))
 
 
 # ------------------------------------------------------------------------------------------------------- census helpers
