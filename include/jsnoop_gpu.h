@@ -340,6 +340,46 @@ uint64_t     jsnoop_batch_pixels(const JsnoopBatch*);                           
  * passes, second attempts at damaged files) is not part of it.  Host arithmetic only.                                                        */
 uint64_t     jsnoop_batch_device_bytes(const JsnoopBatch*);
 
+/* ---- pack: DIBs of a decoded batch -> caller-owned DEVICE memory as cropped, top-down, three-channel pixels ----------------------
+ * The DIB is the reference's CDIB: bottom-up, BGRA with A = 0, img_x x img_y rounded up to whole MCUs.  jsnoop_batch_pack rearranges
+ * any subset of a decoded batch in ONE kernel launch: output pixel (x, y) of image i, 0 <= x < dim_x, 0 <= y < dim_y (the SOF
+ * dimensions), is DIB pixel (x, img_y - 1 - y).  Channels in output order c = 0..2 are R, G, B, or B, G, R with bgr != 0.
+ *   JSNOOP_PACK_HWC: element (x, y, c) at ptr + y * row_pitch + (x * 3 + c) * elem
+ *   JSNOOP_PACK_CHW: element (x, y, c) at ptr + c * plane_pitch + y * row_pitch + x * elem
+ *   JSNOOP_PACK_U8 : elem = 1, the DIB's byte as it is
+ *   JSNOOP_PACK_F32: elem = 4, (float)byte * scale[c] + bias[c]: one rounded fp32 multiply, then one rounded fp32 add (no FMA)
+ * Pitches are in bytes; 0 = dense (row_pitch: dim_x * 3 * elem for HWC, dim_x * elem for CHW; plane_pitch: dim_y * row_pitch; HWC
+ * ignores plane_pitch).  Only the addressed elements are written: the bytes between the dense row and row_pitch keep their content.
+ *
+ * Ordering: the launch is enqueued on the batch's stream, behind the decode enqueued last (both halves of a two-stream decode
+ * included), and the call returns without waiting: the destination is ready once that stream has passed the pack (jsnoop_batch_sync,
+ * or the caller's own event on the stream it gave jsnoop_batch_create).  Damaged files are repaired at jsnoop_batch_sync: a pack
+ * enqueued AFTER jsnoop_batch_sync sees the repaired DIB, one enqueued BEFORE it sees what the parallel path left.
+ * The pack never decodes again: jsnoop_batch_last_form is the same before and after.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: a NULL or not yet decoded batch; an image index out of
+ * range; an image without a decoded DIB (the text names it -- every image of a decoded batch has one, so for images a batch accepted
+ * only the batch-level check can fire); a NULL destination pointer; a row_pitch or plane_pitch below the dense size; JSNOOP_PACK_F32
+ * with a pointer or pitch that is not a multiple of 4; an unknown layout, dtype or struct_size.  n == 0 is 0.                        */
+#define JSNOOP_PACK_HWC 0
+#define JSNOOP_PACK_CHW 1
+#define JSNOOP_PACK_U8  0
+#define JSNOOP_PACK_F32 1
+typedef struct JsnoopPackSpec {
+    uint32_t struct_size;           /* sizeof(JsnoopPackSpec) of the caller, read like JsnoopTuning's: shorter is accepted (the fields it lacks
+                                       are the defaults), longer is refused                                                               */
+    int32_t  layout, dtype, bgr;    /* JSNOOP_PACK_HWC / _CHW, JSNOOP_PACK_U8 / _F32, 0 = R,G,B                                            */
+    float    scale[3], bias[3];     /* JSNOOP_PACK_F32 only, by OUTPUT channel; defaults 1 and 0                                           */
+} JsnoopPackSpec;
+typedef struct JsnoopPackDst { void* ptr; uint64_t row_pitch, plane_pitch; } JsnoopPackDst;   /* device pointer; bytes; 0 = dense */
+void         jsnoop_pack_spec_defaults(JsnoopPackSpec* out);
+/* dense size in bytes of image i's output under `spec` (dim_x * dim_y * 3 * elem); host arithmetic; 0 for a bad argument */
+uint64_t     jsnoop_batch_pack_bytes(const JsnoopBatch*, const JsnoopPackSpec* spec, int i);
+/* images: n indices into the batch, in any order (NULL = images 0..n-1); dst: n destinations */
+int          jsnoop_batch_pack(JsnoopBatch*, const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);
+/* the device the batch lives on (jsnoop_set_device when it was created): where the destinations of jsnoop_batch_pack must be; -1 for NULL */
+int          jsnoop_batch_device(const JsnoopBatch*);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

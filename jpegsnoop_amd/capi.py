@@ -45,6 +45,21 @@ class JobStats(C.Structure):
                 ("max_round_device_bytes", C.c_uint64), ("wall_ms", C.c_double), ("shard_ms", C.c_double * JOB_MAX_SHARDS)]
 
 
+PACK_HWC, PACK_CHW = 0, 1
+PACK_U8, PACK_F32 = 0, 1
+
+
+class PackSpec(C.Structure):
+    """JsnoopPackSpec of include/jsnoop_gpu.h: what jsnoop_batch_pack writes (layout, element type, channel order, float scale / bias)."""
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("dtype", C.c_int32), ("bgr", C.c_int32),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class PackDst(C.Structure):
+    """JsnoopPackDst of include/jsnoop_gpu.h: one destination in device memory; pitches in bytes, 0 = dense."""
+    _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -165,6 +180,10 @@ SIGNATURES = {
     "jsnoop_pipeline_run": (_i, [_p, _i, _i, C.POINTER(C.c_double)]),
     "jsnoop_batch_pixels": (C.c_uint64, [_p]),
     "jsnoop_batch_device_bytes": (C.c_uint64, [_p]),
+    "jsnoop_pack_spec_defaults": (None, [C.POINTER(PackSpec)]),
+    "jsnoop_batch_pack_bytes": (C.c_uint64, [_p, C.POINTER(PackSpec), _i]),
+    "jsnoop_batch_pack": (_i, [_p, C.POINTER(PackSpec), _PI, _i, C.POINTER(PackDst)]),
+    "jsnoop_batch_device": (_i, [_p]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),
@@ -190,6 +209,16 @@ def load(require_device: bool = True) -> C.CDLL:
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `make -C jpegsnoop_amd/csrc` (or __graft_entry__.build()). "
                 "jpegsnoop_amd has no CPU fallback.")
+        # torch first, where it is installed (README.md, "torch and the HIP runtime"): a PyTorch-ROCm wheel brings a HIP runtime of its own, a process drives the
+        # GPU through ONE runtime, the library binds to the one that is loaded first, and torch cannot initialise its device behind another one.  In this
+        # order both use the same runtime -- what bench.py has always done -- and JpegBatch.to_torch can hand torch's memory to the library.
+        # JSNOOP_TORCH_FIRST=0 opts out (the library then binds to the runtime it was linked against, and to_torch cannot be used in the process);
+        # a torch that is absent or does not import leaves a load that works as before.
+        if os.environ.get("JSNOOP_TORCH_FIRST", "1") != "0":
+            try:
+                import torch  # noqa: F401
+            except Exception:
+                pass
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -251,6 +251,10 @@ public:
     bool     BatchSetSplit(int nParts) { return jsnoop_batch_set_split(m_b, nParts) == 0; }   // 0: the library decides (default), 1: one stream, 2: the halves of the batch on two streams side by side (same results)
     bool     BatchSetTuning(const JsnoopTuning& t) { return jsnoop_batch_set_tuning(m_b, &t) == 0; }   // how the batch decodes, never what it produces (jsnoop_tuning_defaults fills a struct)
     const void* BatchBitmapDevicePtr(int nFileInd) const { return jsnoop_batch_dib_dev(m_b, nFileInd); }
+    // the DIBs of the listed files as cropped, top-down, three-channel pixels in the caller's device memory, one launch for the whole list
+    // (jsnoop_batch_pack: enqueued on the batch's stream, not waited for; jsnoop_pack_spec_defaults fills a spec)
+    bool     BatchPack(const JsnoopPackSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
     bool     BatchGetBitmap(int nFileInd, std::vector<uint8_t>& dib, unsigned& nX, unsigned& nY)
     {
         unsigned info[16]; if (jsnoop_batch_image_info(m_b, nFileInd, info)) return false;

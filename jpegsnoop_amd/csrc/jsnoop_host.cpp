@@ -300,6 +300,9 @@ JsnoopBatch::~JsnoopBatch()
     if (d2h_land) hipHostFree(d2h_land);
     if (h_desc) hipHostFree(h_desc);
     if (ev_up) hipEventDestroy(ev_up);
+    if (h_pack) hipHostFree(h_pack);
+    if (d_pack) hipFree(d_pack);
+    if (ev_pack) hipEventDestroy(ev_pack);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     for (auto& e : ev2) if (e) hipEventDestroy(e);
     for (auto& e : aux_ev) if (e) hipEventDestroy(e);

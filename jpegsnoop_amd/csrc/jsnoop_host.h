@@ -122,6 +122,10 @@ struct JsnoopBatch {
     uint8_t* d2h_land = nullptr;                                  // page-locked landing buffer of the read-back calls (32 MiB, on first use)
     uint8_t* h_desc = nullptr; size_t h_desc_cap = 0; hipEvent_t ev_up = nullptr;   // page-locked staging block of the descriptors (upload), the event behind its copies
     int  d2h_staged(void* dst, const void* src, size_t bytes);
+    // jsnoop_batch_pack: the records and the prefix table of one call go through a page-locked block of this batch (h_pack -> d_pack, one copy on the batch stream);
+    // ev_pack is recorded behind that copy and the next pack waits for it before it rewrites the block (the discipline of h_desc / ev_up)
+    uint8_t* h_pack = nullptr; size_t h_pack_cap = 0; uint8_t* d_pack = nullptr; size_t d_pack_cap = 0; hipEvent_t ev_pack = nullptr;
+    int  pack(const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);   // jsnoop_pack.cpp
     JsDeviceArenas dev; JsArenaCaps cap;
     bool uploaded;
     uint32_t us_ticket_base[2] = { 0, 0 };                        // value of the two chunk-ticket counters (behind us_state; one per part of a split decode) before the next launch

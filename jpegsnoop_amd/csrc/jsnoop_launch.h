@@ -83,3 +83,7 @@ void js_launch_tail_pass(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab
                          uint32_t us_wg0, uint32_t us_wgs, uint32_t sy_wg0, uint32_t sy_wgs, const JsTableSet* tables, const uint8_t* raw,
                          const uint32_t* chunk_keep, const uint32_t* chunk_rst, const uint8_t* ustr, uint32_t* seg_tab, uint32_t* side, uint32_t* sub, uint64_t nsub,
                          int16_t* coef, int16_t* dccum, uint8_t* mcu_rst, uint32_t* mcu_pos, uint32_t* us_out, const uint32_t* flags /*the batch's flag arena*/, const uint32_t* sel1 /*device: the image index*/);
+// k_pack_rgb (jsnoop_pack.hip): DIBs of a decoded batch -> caller-owned device memory, cropped top-down three-channel pixels, ONE launch for the whole list.
+// recs / unit_base: JsPackRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error.
+int  js_launch_pack_rgb(hipStream_t st, const JsImage* imgs, const uint8_t* dib, const JsPackRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                        int layout /*JSNOOP_PACK_HWC / _CHW*/, int dtype /*JSNOOP_PACK_U8 / _F32*/, const JsPackArgs& a);

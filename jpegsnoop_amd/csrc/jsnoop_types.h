@@ -139,3 +139,9 @@ static inline uint32_t js_tile_bytes(const JsImage& im)
 }
 
 static inline __host__ __device__ uint32_t js_side_words(uint32_t nmcu, uint32_t nblk) { return JS_SIDE_MCUMAP + nmcu + 3 * ((nblk + 1) / 2); }
+
+// jsnoop_batch_pack (k_pack_rgb): one record per listed image, and a prefix table unit_base[nrec + 1] over the records in which image k owns
+// dim_y * ceil(dim_x / JS_PACK_SEG) units -- a unit is one segment of one output row, the work of one wave at a time.
+#define JS_PACK_SEG 512u             /* pixels per unit: two 16-byte loads per lane */
+struct JsPackRec  { uint32_t img, reserved; uint64_t ptr, row_pitch, plane_pitch; };   // destination of image `img`; pitches in bytes, resolved (never 0)
+struct JsPackArgs { int32_t bgr; float scale[3], bias[3]; };

@@ -155,6 +155,7 @@ class JpegBatch:
         self._lib.jsnoop_batch_set_options(self._h, int(decode_ac), int(want_planes), int(force_exact))
         self.want_planes = want_planes
         self._borrowed = False                   # True: the handle belongs to a JpegPipeline, which destroys it
+        self._stream = int(stream) if stream else None   # the caller's hipStream_t, or None: the batch runs on a stream of its own
 
     def close(self):
         if self._h:
@@ -218,6 +219,114 @@ class JpegBatch:
         out = np.empty((inf["img_y"], inf["img_x"], 4), np.uint8)
         self._chk(self._lib.jsnoop_batch_read_dib(self._h, i, out.ctypes.data), "batch_read_dib")
         return out
+
+    def device(self) -> int:
+        """The device the batch lives on (jsnoop_batch_device)."""
+        return int(self._lib.jsnoop_batch_device(self._h))
+
+    def pack_bytes(self, i, layout="CHW", float32=False) -> int:
+        """Dense size in bytes of image i's packed output (jsnoop_batch_pack_bytes)."""
+        spec = _pack_spec(self._lib, layout, bool(float32), False, None, None)
+        return int(self._lib.jsnoop_batch_pack_bytes(self._h, C.byref(spec), i))
+
+    def to_torch(self, images=None, layout="CHW", dtype=None, bgr=False, scale=None, bias=None, stack=False, pad_to=None, out=None):
+        """The decoded images as torch tensors on the batch's device: cropped to the SOF dimensions, top-down, three channels (R,G,B, or
+        B,G,R with bgr), filled by ONE jsnoop_batch_pack -- no pixel crosses PCIe.
+
+        images: indices into the batch, any order (None = all).  layout "CHW" -> [3, dim_y, dim_x], "HWC" -> [dim_y, dim_x, 3].
+        dtype: torch.uint8 (default: the DIB's bytes) or torch.float32 (float(v) * scale[c] + bias[c], c the output channel; scale / bias a
+        number or three, defaults 1 and 0; one rounded multiply, then one rounded add).
+        Default: a list of tensors, one per image, carved out of one allocation.  stack=True: one [N, ...] tensor (ValueError if the dimensions
+        differ).  pad_to=(H, W): one zero-filled [N, 3, H, W] / [N, H, W, 3] tensor, every image in its top-left corner.  out=: a tensor
+        [N, ...] at least as large as every image, or a list of tensors of the images' exact shapes; inner dimensions contiguous; returned as it is.
+
+        Calls sync() first (damaged files arrive repaired), synchronises torch's current stream before the pack unless the batch runs on it, and
+        waits for the batch's stream -- sync() again, no other stream of the device is waited for -- before it returns: the tensors are ready."""
+        import torch
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"to_torch: image index {i} out of range, the batch holds {n_all}")
+        if dtype is None:
+            dtype = torch.uint8
+        if dtype not in (torch.uint8, torch.float32):
+            raise ValueError("to_torch: dtype must be torch.uint8 or torch.float32")
+        is_f32 = dtype == torch.float32
+        if not is_f32 and (scale is not None or bias is not None):
+            raise ValueError("to_torch: scale / bias belong to dtype=torch.float32")
+        if bool(stack) + (pad_to is not None) + (out is not None) > 1:
+            raise ValueError("to_torch: stack, pad_to and out exclude each other")
+        spec = _pack_spec(self._lib, layout, is_f32, bgr, scale, bias)
+        chw = layout == "CHW"
+        self.sync()
+        dev = torch.device("cuda", self.device())
+        dims = []
+        for i in idx:
+            inf = self.info(i)
+            dims.append((inf["dim_y"], inf["dim_x"]))
+        shape = (lambda h, w: (3, h, w)) if chw else (lambda h, w: (h, w, 3))
+        crop = (lambda t, h, w: t[:, :h, :w]) if chw else (lambda t, h, w: t[:h, :w, :])
+        if out is not None:
+            if isinstance(out, torch.Tensor):
+                if out.dim() != 4 or out.shape[0] != len(idx) or out.shape[1 if chw else 3] != 3:
+                    raise ValueError(f"to_torch: out must be [{len(idx)}, " + ("3, H, W]" if chw else "H, W, 3]") + f", got {list(out.shape)}")
+                H, W = (out.shape[2], out.shape[3]) if chw else (out.shape[1], out.shape[2])
+                for k, (h, w) in enumerate(dims):
+                    if h > H or w > W:
+                        raise ValueError(f"to_torch: image {idx[k]} is {h} x {w}, larger than out's {H} x {W}")
+                views, result = [crop(out[k], h, w) for k, (h, w) in enumerate(dims)], out
+            else:
+                views, result = list(out), out
+                if len(views) != len(idx):
+                    raise ValueError(f"to_torch: out holds {len(views)} tensors for {len(idx)} images")
+                for k, (h, w) in enumerate(dims):
+                    if not isinstance(views[k], torch.Tensor) or tuple(views[k].shape) != shape(h, w):
+                        raise ValueError(f"to_torch: out[{k}] must be a tensor of shape {list(shape(h, w))} for image {idx[k]}")
+            for k, t in enumerate(views):
+                if t.device != dev:
+                    raise ValueError(f"to_torch: out[{k}] is on {t.device}, the batch on {dev}")
+                if t.dtype != dtype:
+                    raise ValueError(f"to_torch: out[{k}] is {t.dtype}, asked for {dtype}")
+        elif pad_to is not None:
+            H, W = int(pad_to[0]), int(pad_to[1])
+            for k, (h, w) in enumerate(dims):
+                if h > H or w > W:
+                    raise ValueError(f"to_torch: image {idx[k]} is {h} x {w}, larger than pad_to = ({H}, {W})")
+            result = torch.zeros((len(idx),) + shape(H, W), dtype=dtype, device=dev)
+            views = [crop(result[k], h, w) for k, (h, w) in enumerate(dims)]
+        elif stack:
+            for k, d in enumerate(dims):
+                if d != dims[0]:
+                    raise ValueError(f"to_torch: stack=True, but image {idx[k]} is {d[0]} x {d[1]} and image {idx[0]} is {dims[0][0]} x {dims[0][1]}")
+            result = torch.empty((len(idx),) + (shape(*dims[0]) if dims else shape(0, 0)), dtype=dtype, device=dev)
+            views = [result[k] for k in range(len(idx))]
+        else:
+            flat = torch.empty(sum(3 * h * w for h, w in dims), dtype=dtype, device=dev)
+            views, off = [], 0
+            for h, w in dims:
+                views.append(flat[off:off + 3 * h * w].view(shape(h, w)))
+                off += 3 * h * w
+            result = views
+        if not idx:
+            return result
+        elem = 4 if is_f32 else 1
+        dst = (capi.PackDst * len(idx))()
+        for k, t in enumerate(views):
+            st = t.stride()
+            if st[2] != 1 or (not chw and st[1] != 3) or min(st) < 1:
+                raise ValueError(f"to_torch: destination {k}: the inner dimensions must be contiguous (strides {st})")
+            dst[k].ptr = t.data_ptr()
+            dst[k].row_pitch = (st[1] if chw else st[0]) * elem
+            dst[k].plane_pitch = st[0] * elem if chw else 0
+        # memory the allocator hands out may still have work pending on torch's current stream (the zero fill of pad_to among it)
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        ind = (C.c_int * len(idx))(*idx)
+        self._chk(self._lib.jsnoop_batch_pack(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack")
+        self.sync()                              # waits for the batch's stream alone
+        return result
 
     def color_stats(self, i, histo_en=True):
         """bHistoEn (or only bStatClipEn) statistics of image i: the JSNOOP_STATS_WORDS record of include/jsnoop_gpu.h."""
@@ -296,7 +405,7 @@ class JpegPipeline:
         self.slots = []
         for i in range(slots):
             b = JpegBatch.__new__(JpegBatch)
-            b._lib, b._h, b.want_planes, b._borrowed = self._lib, self._lib.jsnoop_pipeline_slot(self._h, i), False, True
+            b._lib, b._h, b.want_planes, b._borrowed, b._stream = self._lib, self._lib.jsnoop_pipeline_slot(self._h, i), False, True, None
             self.slots.append(b)
 
     def run(self, batches, d2h=False):
@@ -319,6 +428,25 @@ class JpegPipeline:
             pass
 
 
+def _pack_spec(lib, layout, is_f32, bgr, scale, bias) -> "capi.PackSpec":
+    if layout not in ("CHW", "HWC"):
+        raise ValueError("layout must be \"CHW\" or \"HWC\"")
+    spec = capi.PackSpec()
+    lib.jsnoop_pack_spec_defaults(C.byref(spec))
+    spec.layout = capi.PACK_CHW if layout == "CHW" else capi.PACK_HWC
+    spec.dtype = capi.PACK_F32 if is_f32 else capi.PACK_U8
+    spec.bgr = int(bool(bgr))
+    for name, val in (("scale", scale), ("bias", bias)):
+        if val is None:
+            continue
+        vals = [float(val)] * 3 if np.isscalar(val) else [float(v) for v in val]
+        if len(vals) != 3:
+            raise ValueError(f"{name} must be a number or three numbers")
+        for c in range(3):
+            getattr(spec, name)[c] = vals[c]
+    return spec
+
+
 _INFO_KEYS = "dim_x dim_y img_x img_y mcu_w mcu_h mcu_xmax mcu_ymax blk_xmax blk_ymax scan_bytes flags path ncomp file_len total_blocks".split()
 
 
@@ -339,7 +467,16 @@ class JobFileResult:
         if f.batch:
             b = JpegBatch.__new__(JpegBatch)
             b._lib, b._h, b.want_planes, b._borrowed = lib, f.batch, want_planes, True
+            b._stream = None
             self.batch = b
+
+    def to_torch(self, **kw):
+        """JpegBatch.to_torch for this file alone: one tensor ([3, dim_y, dim_x] / [dim_y, dim_x, 3]; with stack / pad_to / a tensor out, the
+        [1, ...] tensor).  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("to_torch: this result holds no resident image (status %s)" % self.status)
+        r = self.batch.to_torch(images=[self.image], **kw)
+        return r[0] if isinstance(r, list) else r
 
     def __repr__(self):
         return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
