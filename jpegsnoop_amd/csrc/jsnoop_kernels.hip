@@ -2931,6 +2931,39 @@ __global__ void __launch_bounds__(THREADS) k_block_scan(const JsImage* __restric
     if (threadIdx.x == 0) { side[im.side_off + 14] = tot; if (tot < im.total_blocks) { FLAG_OR(flags, img, F_SHORT); ANOM_MIN(flags, img, ANOM_KEY(tot, AK_MIRROR)); } }
 }
 
+// ---- what every form of the write pass does around its walk: k_write, and write_walk (k_write2, k_write_dc) ----
+// Entry state of a lane: it enters where the walk in front of it left -- position p0, state word s0 -- at block `blk` of the image.  Only an
+// `active` lane walks (its cursor is set up here); the others report what they were handed, or nothing.
+struct WalkEntry { uint32_t blk = 0, seg = 0, c = 0, k = 0, seg_end = 0, res_p = 0, res_s = 0; bool verify = false, check_n = false, active = false, skip = false; };
+__device__ __forceinline__ Cursor cur_idle(const uint32_t* words) { Cursor c; c.words = words; c.widx = 0; c.poff = 0; c.w0 = c.w1 = c.nxt = 0; c.sh = 0; c.p = 0; return c; }
+template <int WL>
+__device__ __forceinline__ WalkEntry walk_entry(uint32_t p0, uint32_t s0, uint32_t blk, uint32_t own_end, uint32_t total_bits, uint32_t nseg, uint32_t nblocks,
+                                                const uint32_t* __restrict__ st, Cursor& cur)
+{
+    WalkEntry E; E.blk = blk; E.seg = ST_SEG(s0); E.c = ST_C(s0); E.k = ST_K(s0);
+    E.verify = true;
+    if (p0 != P_END && p0 >= own_end) { E.res_p = p0; E.res_s = s0; }                          // owns no symbol: passes through
+    else if (p0 == P_END || (p0 >= total_bits && E.seg + 1 >= nseg)) { E.res_p = P_END; E.res_s = 0; E.check_n = true; }
+    else if (blk >= nblocks) E.verify = false;                                                  // everything owned lies past the last MCU
+    else { E.active = true; E.check_n = true; E.seg_end = st[E.seg + 1] * 8; E.skip = E.k != 0; cur_init<WL>(cur, cur.words, p0); }
+    return E;
+}
+// Verification of a lane that entered with `verify`: the chain must be at its fixed point (want_p / want_s: the exit state on record), and
+// the block count that fed the prefix sum must be the real one.  res_*: what the lane captured at the end of its own range; one that never
+// got there reports where it stands (p, state).  want_n is read only where it is checked.  Returns the flag to raise.
+__device__ __forceinline__ uint32_t walk_verify(bool check_n, bool captured, uint32_t res_p, uint32_t res_s, uint32_t res_n, uint32_t p, uint32_t state, uint32_t nblk,
+                                                uint32_t want_p, uint32_t want_s, uint32_t want_n)
+{
+    if (check_n && !captured && res_p != P_END) { res_p = p; res_s = p == P_END ? 0u : state; res_n = nblk; }
+    return (res_p != want_p || res_s != want_s || (check_n && res_n != want_n)) ? F_NOSYNC : 0u;
+}
+// The workgroup's code-length histogram (m_anDhtHisto) goes from LDS into the image's side block.
+__device__ __forceinline__ void histo_spill(const uint32_t* s_histo, uint32_t* __restrict__ ho)
+{
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < 2 * 4 * 17; q += SY_THREADS) { const uint32_t v = s_histo[q]; if (v) atomicAdd(&ho[q], v); }
+}
+
 // WRITE pass.  Every 8x8 block is written by exactly one lane -- the one that decodes its DC symbol.  A lane entering
 // mid-block (k > 0) parses the rest of that block without output; a lane whose last block is unfinished at the end
 // of its sub-sequence keeps decoding past it until the block completes.  Coefficients are dequantised
@@ -2979,20 +3012,12 @@ __global__ void __launch_bounds__(SY_THREADS) k_write(const JsImage* __restrict_
     const uint32_t nblocks = im.total_blocks, decode_ac = im.decode_ac, prec_shift = im.precision >= 8 ? ((im.precision - 8) & 31) : 0;
     const bool in_data = i * SUB_BITS < total_bits;
     const size_t g = im.subseq_off + i;
-    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = 0, c = 0, k = 0, seg_end = 0, blk = 0;
-    uint32_t res_p = 0, res_s = 0, res_n = 0;                // what this lane reports for verification
-    bool verify = false, check_n = false, active = false, captured = false, skip = false;
     const uint32_t own_end = min((i + 1) * SUB_BITS, total_bits);
-    Cursor cur; cur.words = words; cur.widx = 0; cur.poff = 0; cur.w0 = cur.w1 = cur.nxt = 0; cur.sh = 0; cur.p = 0;
-    if (in_data) {
-        const uint32_t p0 = i ? A.out_p[g - 1] : 0u, s0 = i ? A.out_s[g - 1] : 0u;
-        blk = A.base[g]; seg = ST_SEG(s0); c = ST_C(s0); k = ST_K(s0);
-        verify = true;
-        if (p0 != P_END && p0 >= own_end) { res_p = p0; res_s = s0; }                          // owns no symbol: passes through
-        else if (p0 == P_END || (p0 >= total_bits && seg + 1 >= nseg)) { res_p = P_END; res_s = 0; check_n = true; }
-        else if (blk >= nblocks) verify = false;                                                // everything owned lies past the last MCU
-        else { active = true; check_n = true; seg_end = st[seg + 1] * 8; skip = k != 0; cur_init<WL>(cur, words, p0); }
-    }
+    Cursor cur = cur_idle(words); WalkEntry E;
+    if (in_data) E = walk_entry<WL>(i ? A.out_p[g - 1] : 0u, i ? A.out_s[g - 1] : 0u, A.base[g], own_end, total_bits, nseg, nblocks, st, cur);
+    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = E.seg, c = E.c, k = E.k, seg_end = E.seg_end, blk = E.blk;
+    uint32_t res_p = E.res_p, res_s = E.res_s, res_n = 0;    // what this lane reports for verification
+    bool active = E.active, captured = false, skip = E.skip;
     int16_t dq0 = 0;
     const uint32_t wb0 = W.wb0, wb1 = W.wb1, wb2 = W.wb2;       // per component: byte offset of its DC row | of its AC row << 16
     const char* l1b = W.rows;
@@ -3130,20 +3155,13 @@ __global__ void __launch_bounds__(SY_THREADS) k_write(const JsImage* __restrict_
             }
         }
     }
-    if (verify) {
-        if (check_n && !captured && res_p != P_END) { res_p = cur.p; res_s = cur.p == P_END ? 0u : ST_MAKE(seg, c, k); res_n = nblk; }
-        // the chain must be at its fixed point, and the block count that fed the prefix sum must be the real one
-        if (res_p != A.out_p[g] || res_s != A.out_s[g] || (check_n && res_n != A.nblk[g])) fl |= F_NOSYNC;
-    }
-    if (SIDE) {
-        __syncthreads();
-        uint32_t* ho = side + im.side_off + JS_SIDE_HISTO;
-        for (uint32_t q = threadIdx.x; q < 2 * 4 * 17; q += SY_THREADS) { const uint32_t v = s_histo[q]; if (v) atomicAdd(&ho[q], v); }
-    } else if (fl) { FLAG_OR(flags, img, fl); if (an != 0xFFFFFFFFu) ANOM_MIN(flags, img, an); }
+    if (E.verify) fl |= walk_verify(E.check_n, captured, res_p, res_s, res_n, cur.p, ST_MAKE(seg, c, k), nblk, A.out_p[g], A.out_s[g], E.check_n ? A.nblk[g] : 0u);
+    if (SIDE) histo_spill(s_histo, side + im.side_off + JS_SIDE_HISTO);
+    else if (fl) { FLAG_OR(flags, img, fl); if (an != 0xFFFFFFFFu) ANOM_MIN(flags, img, an); }
 }
 
 // WRITE pass, second form (the one the main path launches; k_write<., true> above stays the side-output pass and k_write<., false> the
-// cross-check, JSNOOP_WRITE_V1=1).  Same walk, same results -- written against the instruction-cost table of DESIGN.md §4.7:
+// cross-check, JSNOOP_WRITE_V1=1).  Same walk, same results -- written against the instruction-cost table of HISTORY.md §4.7:
 //  * every per-lane flag that lives across steps (active, skip, captured) is a 64-bit lane MASK in scalar registers; votes are compares
 //    written straight into a scalar pair and combined there, a lane reads its bit back as a predicate (inverse ballot) -- the compiler
 //    never has to turn a flag into 0 / 1 in a vector register and compare it again;
@@ -3162,22 +3180,26 @@ __device__ __forceinline__ int32_t extend_bits(uint32_t win, uint32_t skipbits, 
     const uint32_t neglim = (0xFFFFFFFFu << size) + 1u;          // -(2^size - 1)
     return (int32_t)x < 0 ? (int32_t)vraw : (int32_t)(vraw + neglim);
 }
+// The walk of the second form: the body of k_write2 and of k_write_dc, which differ in what becomes of a coefficient and in nothing else.
 // HALF (small jobs after the candidate synchronisation): two lanes per sub-sequence -- the second one enters at the state the selected memo
 // walk reported for the middle of the sub-sequence (half_*: position, state word, blocks completed before it) -- twice the lanes, half the steps of
 // the chain a wave is; the lane of the first half verifies against that middle state, the other one against the exit state as before.
 // REC (a single-image call that will ask for the side outputs anyway, js_side_prepare): the pass also records what the side walk (k_write<., true>) would -- the bit
 // position of every MCU top and of the image's last block top in rec_pos, the code-length histogram (m_anDhtHisto) into the side block -- and that walk is not run.
-template <int WL, bool HALF = false, bool REC = false>
-__global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
-                                                       const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
-                                                       const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
-                                                       int16_t* __restrict__ coef, int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
-                                                       uint32_t tab_rows, uint32_t tab_lut2, const uint32_t* __restrict__ half_p = nullptr, const uint32_t* __restrict__ half_s = nullptr,
-                                                       const uint32_t* __restrict__ half_n = nullptr, uint32_t* __restrict__ rec_pos = nullptr)
+// DC (the DC-only fast form: every image of the launch has decode_ac == 0 and goes on to k_dc_color): nothing that serves the coefficient
+// arena -- no lane-private block in LDS (s_blk is null), no zeroing, no de-zigzag store, no value of the second symbol, no flush; AC symbols are
+// parsed, and what a block leaves is its dequantised DC difference, from one of three DC quantisers held in registers.  Entry states, steps,
+// walk_slow at interval ends, flags, anomaly keys, restart marks, the DC queue into dccum and the verification are the one text below.
+template <int WL, bool HALF, bool REC, bool DC>
+__device__ __forceinline__ void write_walk(int16_t (*s_blk)[WR_STRIDE], uint32_t* s_histo, const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
+                                           const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
+                                           const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
+                                           int16_t* __restrict__ coef, int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
+                                           uint32_t tab_rows, uint32_t tab_lut2, const uint32_t* __restrict__ half_p, const uint32_t* __restrict__ half_s,
+                                           const uint32_t* __restrict__ half_n, uint32_t* __restrict__ rec_pos)
 {
+    static_assert(!DC || (!HALF && !REC), "the DC-only form: one lane per sub-sequence, no side outputs");
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-    __shared__ __attribute__((aligned(16))) int16_t s_blk[SY_THREADS][WR_STRIDE];
-    __shared__ uint32_t s_histo[REC ? 2 * 4 * 17 : 1];
     const uint32_t wg = (HALF ? blockIdx.x >> 1 : blockIdx.x) + sy_base[0];
     const uint32_t img = find_image(sy_base, nimg, wg);
     const JsImage& im = imgs[img];
@@ -3194,37 +3216,32 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
     const JsTableSet& tset = tables[im.tableset];
     SubTabs T; T.nb = im.blk_per_mcu; T.n1 = im.samp_h[1] * im.samp_v[1]; T.n2 = im.ncomp == 3 ? T.n1 + im.samp_h[2] * im.samp_v[2] : T.nb;
     WriteTabs W; load_wtabs(W, s_dyn, tset, tab_rows, tab_lut2, im.ncomp, threadIdx.x, SY_THREADS);
-    { uint32_t* z = reinterpret_cast<uint32_t*>(s_blk[threadIdx.x]); for (int j = 0; j < WR_STRIDE / 2; j++) z[j] = 0u; }
+    char* lbuf = nullptr;                                        // the lane's block in LDS
+    if constexpr (!DC) { lbuf = reinterpret_cast<char*>(s_blk[threadIdx.x]); uint32_t* z = reinterpret_cast<uint32_t*>(lbuf); for (int j = 0; j < WR_STRIDE / 2; j++) z[j] = 0u; }
     if (REC) for (uint32_t q = threadIdx.x; q < 2 * 4 * 17; q += SY_THREADS) s_histo[q] = 0;
     __syncthreads();
 
     const uint32_t* words = reinterpret_cast<const uint32_t*>(ustr + im.ustr_off);
     const uint32_t* st = seg_tab + im.seg_off;
-    int16_t* cbase = coef + im.coef_off * 64; int16_t* dbase = dccum + im.coef_off; uint8_t* rstf = mcu_rst + im.mcu_off;
-    char* lbuf = reinterpret_cast<char*>(s_blk[threadIdx.x]);
+    int16_t* cbase = DC ? nullptr : coef + im.coef_off * 64; int16_t* dbase = dccum + im.coef_off; uint8_t* rstf = mcu_rst + im.mcu_off;
     const uint32_t nblocks = im.total_blocks, prec_shift = im.precision >= 8 ? ((im.precision - 8) & 31) : 0;
-    const uint64_t acmask = im.decode_ac ? ~0ull : 0ull;        // DC-only mode: AC coefficients are parsed, not stored
+    [[maybe_unused]] uint64_t acmask = 0ull;                     // !DC: all lanes where the image wants its AC coefficients stored (DC-only mode: parsed, not stored)
+    if constexpr (!DC) acmask = im.decode_ac ? ~0ull : 0ull;
     const bool in_data = i * SUB_BITS + hi * (SUB_BITS / 2) < total_bits;
     const size_t g = im.subseq_off + i;
-    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = 0, c = 0, k = 0, seg_end = 0, blk = 0;
-    uint32_t res_p = 0, res_s = 0, res_n = 0;                // what this lane reports for verification
-    bool verify = false, check_n = false, active0 = false, skip0 = false;
     const uint32_t own_end = min(HALF && !hi ? i * SUB_BITS + SUB_BITS / 2 : (i + 1) * SUB_BITS, total_bits);
-    Cursor cur; cur.words = words; cur.widx = 0; cur.poff = 0; cur.w0 = cur.w1 = cur.nxt = 0; cur.sh = 0; cur.p = 0;
-    if (in_data) {
-        const uint32_t p0 = hi ? half_p[g] : (i ? A.out_p[g - 1] : 0u), s0 = hi ? half_s[g] : (i ? A.out_s[g - 1] : 0u);
-        blk = A.base[g] + (hi ? half_n[g] : 0u); seg = ST_SEG(s0); c = ST_C(s0); k = ST_K(s0);
-        verify = true;
-        if (p0 != P_END && p0 >= own_end) { res_p = p0; res_s = s0; }                          // owns no symbol: passes through
-        else if (p0 == P_END || (p0 >= total_bits && seg + 1 >= nseg)) { res_p = P_END; res_s = 0; check_n = true; }
-        else if (blk >= nblocks) verify = false;                                                // everything owned lies past the last MCU
-        else { active0 = true; check_n = true; seg_end = st[seg + 1] * 8; skip0 = k != 0; cur_init<WL>(cur, words, p0); }
-    }
+    Cursor cur = cur_idle(words); WalkEntry E;
+    if (in_data) E = walk_entry<WL>(hi ? half_p[g] : (i ? A.out_p[g - 1] : 0u), hi ? half_s[g] : (i ? A.out_s[g - 1] : 0u), A.base[g] + (hi ? half_n[g] : 0u),
+                                    own_end, total_bits, nseg, nblocks, st, cur);
+    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = E.seg, c = E.c, k = E.k, seg_end = E.seg_end, blk = E.blk;
+    uint32_t res_p = E.res_p, res_s = E.res_s, res_n = 0;    // what this lane reports for verification
     const uint32_t wb0 = W.wb0, wb1 = W.wb1, wb2 = W.wb2;       // per component: byte offset of its DC row | of its AC row << 16
     const char* l1b = W.rows;
     const char* qzb = reinterpret_cast<const char*>(W.qz);
+    uint32_t qd0 = 0, qd1 = 0, qd2 = 0;                         // DC: the three DC quantisers
+    if constexpr (DC) { qd0 = W.qz[0] & 0xFFFFu; qd1 = W.qz[64] & 0xFFFFu; qd2 = W.qz[128] & 0xFFFFu; }
     uint32_t comp = comp_of(T, c), wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
-    uint64_t m_act = WBALLOT(active0), m_skip = WBALLOT(skip0), m_cap = 0ull;
+    uint64_t m_act = WBALLOT(E.active), m_skip = WBALLOT(E.skip), m_cap = 0ull;
     // DC differences of finished blocks wait in registers -- eight per lane, in memory order: the oldest in the low half of dcq0 (a lane's
     // finished blocks have consecutive numbers) -- and leave as ONE 16-byte store of the lanes that hold eight: what the vector memory pipe
     // is charged for is the store instruction, not its bytes (a 2-byte store per block: +0.45 ms per 1024 images; eight 2-byte stores per
@@ -3233,14 +3250,6 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
     // except a first one it entered in the middle (skip) and blocks past the image's last -- after which it flushes none.
     uint32_t dcq0 = 0, dcq1 = 0, dcq2 = 0, dcq3 = 0, dccnt = 0, dclast = 0, dq0 = 0;
     uint32_t rst_blk = 0xFFFFFFFFu;                              // the block in progress when a restart was last followed (see ANOM_KEY): written on the slow path only
-    auto dc_store_rest = [&]() {                                 // what is left at the end: the newest dccnt values sit in the top halves
-        #pragma unroll
-        for (uint32_t h = 0; h < 8; h++) {
-            const uint32_t q = h < 2 ? dcq0 : (h < 4 ? dcq1 : (h < 6 ? dcq2 : dcq3));
-            if (h + dccnt >= 8u) dbase[dclast - 7u + h] = (int16_t)((h & 1u) ? q >> 16 : q);
-        }
-        dccnt = 0;
-    };
     for (;;) {
         // ---- end of the owned range: report the state there; keep going only to finish a block this lane started
         const uint64_t m_end = WBALLOT(cur.p >= own_end) & m_act;
@@ -3285,7 +3294,8 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
         uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & WBALLOT(tot + tot2 <= JS_STEP_BITS) & m_act;
         // ---- anything out of the ordinary sits behind one vote: no code, the end of the interval inside the code or its value
         //      bits, a run past the 64th coefficient
-        uint64_t m_norm = m_act, m_nost = 0ull, m_bad = 0ull;      // m_bad: a code that matches nothing ended the lane's block (walk_slow)
+        uint64_t m_norm = m_act, m_bad = 0ull;                   // m_bad: a code that matches nothing ended the lane's block (walk_slow)
+        [[maybe_unused]] uint64_t m_nost = 0ull;                 // !DC: a run past the 64th coefficient stores nothing
         const uint64_t m_abn = (WBALLOT(len == 0u) | WBALLOT(p1 > seg_end) | WBALLOT(k2 > 64u)) & m_act;
         if (m_abn) {
             const uint64_t m_slow = (WBALLOT(len == 0u) | WBALLOT(cur.p + len > seg_end)) & m_act;
@@ -3312,7 +3322,7 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
             m_bad = WBALLOT(bad) & m_act;
             m_cap |= m_over; m_act &= ~m_over;
             m_norm &= ~m_slow; m_two &= ~m_slow;
-            m_nost = WBALLOT(k2 > 64u);
+            if constexpr (!DC) m_nost = WBALLOT(k2 > 64u);
         }
         if (REC) {                                               // code lengths of what this lane decodes inside its own range (k_write<., true> counts the same symbols)
             const uint32_t hd = tset.dest_id[comp * 2], ha = tset.dest_id[comp * 2 + 1];
@@ -3322,23 +3332,31 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
             }
             if (IBAL(m_bad & ~m_cap) && blk < nblocks) atomicAdd(&s_histo[(IBAL(m_dc) ? hd : 4u + ha) * 17u + 1u], 1u);     // (one bit "used", :1178-1186)
         }
-        // ---- value bits: EXTEND (HuffmanDc2Signed :859), precision divide (:1234-1238), dequantise (:2278), de-zigzag
-        int32_t val = extend_bits(win, len, size), val2 = extend_bits(win2, len2, size2);
-        if (prec_shift) { val /= (int32_t)(1u << prec_shift); val2 /= (int32_t)(1u << prec_shift); }
-        const char* qrow = qzb + comp * 256u;
-        const uint32_t qz = *reinterpret_cast<const uint32_t*>(qrow + (((k2 - 1u) & 63u) << 2));           // DC: 0, AC: k + run
-        const uint32_t qz2 = *reinterpret_cast<const uint32_t*>(qrow + (((k3 - 1u) & 63u) << 2));
-        const uint64_t m_st = m_norm & ~m_skip & ~m_nost & (m_dc | acmask);
-        const uint32_t dq = (uint32_t)((int32_t)(int16_t)val * (int32_t)(qz & 0xFFFFu));
-        if (IBAL(m_st)) *reinterpret_cast<int16_t*>(lbuf + ((qz >> 16) << 1)) = (int16_t)dq;
-        dq0 = IBAL(m_dc & m_norm) ? dq : dq0;                    // the block's DC difference
-        if (m_bad) {
-            if (IBAL(m_bad)) {                                   // the block keeps its DC difference (none decoded yet: 0) and nothing else
-                if (IBAL(m_dc)) dq0 = 0u;
-                if (!IBAL(m_skip)) { uint32_t* z = reinterpret_cast<uint32_t*>(lbuf); for (int j = 0; j < WR_STRIDE / 2; j++) z[j] = 0u; *reinterpret_cast<int16_t*>(lbuf) = (int16_t)dq0; }
+        // ---- value bits: EXTEND (HuffmanDc2Signed :859), precision divide (:1234-1238), dequantise (:2278)
+        int32_t val = extend_bits(win, len, size);
+        [[maybe_unused]] int32_t val2 = 0;                       // !DC: the value of the second symbol
+        if constexpr (!DC) val2 = extend_bits(win2, len2, size2);
+        if (prec_shift) { val /= (int32_t)(1u << prec_shift); if constexpr (!DC) val2 /= (int32_t)(1u << prec_shift); }
+        if constexpr (DC) {                                      // the DC difference alone: AC values are parsed, not formed
+            const uint32_t qd = comp == 0 ? qd0 : (comp == 1 ? qd1 : qd2);
+            dq0 = IBAL(m_dc & m_norm) ? (uint32_t)((int32_t)(int16_t)val * (int32_t)qd) : dq0;
+            if (m_bad) { if (IBAL(m_bad & m_dc)) dq0 = 0u; }      // a code that matches nothing in front of the DC value: the block keeps a zero difference
+        } else {                                                 // both symbols, de-zigzagged into the lane's block
+            const char* qrow = qzb + comp * 256u;
+            const uint32_t qz = *reinterpret_cast<const uint32_t*>(qrow + (((k2 - 1u) & 63u) << 2));           // DC: 0, AC: k + run
+            const uint32_t qz2 = *reinterpret_cast<const uint32_t*>(qrow + (((k3 - 1u) & 63u) << 2));
+            const uint64_t m_st = m_norm & ~m_skip & ~m_nost & (m_dc | acmask);
+            const uint32_t dq = (uint32_t)((int32_t)(int16_t)val * (int32_t)(qz & 0xFFFFu));
+            if (IBAL(m_st)) *reinterpret_cast<int16_t*>(lbuf + ((qz >> 16) << 1)) = (int16_t)dq;
+            dq0 = IBAL(m_dc & m_norm) ? dq : dq0;                // the block's DC difference
+            if (m_bad) {
+                if (IBAL(m_bad)) {                               // the block keeps its DC difference (none decoded yet: 0) and nothing else
+                    if (IBAL(m_dc)) dq0 = 0u;
+                    if (!IBAL(m_skip)) { uint32_t* z = reinterpret_cast<uint32_t*>(lbuf); for (int j = 0; j < WR_STRIDE / 2; j++) z[j] = 0u; *reinterpret_cast<int16_t*>(lbuf) = (int16_t)dq0; }
+                }
             }
+            if (IBAL(m_two & ~m_skip & acmask)) *reinterpret_cast<int16_t*>(lbuf + ((qz2 >> 16) << 1)) = (int16_t)((int32_t)(int16_t)val2 * (int32_t)(qz2 & 0xFFFFu));
         }
-        if (IBAL(m_two & ~m_skip & acmask)) *reinterpret_cast<int16_t*>(lbuf + ((qz2 >> 16) << 1)) = (int16_t)((int32_t)(int16_t)val2 * (int32_t)(qz2 & 0xFFFFu));
         // ---- advance
         const bool two = IBAL(m_two);
         { const uint32_t adv = tot + (two ? tot2 : 0u); cur.sh -= (int32_t)adv; cur.p += adv; }
@@ -3363,205 +3381,33 @@ __global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict
                 blk++;
             }
             m_skip &= ~m_done;
-            // ---- the whole wave moves every block that completed in this step: 8 lanes x 16 bytes per block, eight blocks per store
-            // instruction (round 6; four per instruction before: 3.35 -> 3.23 ms, a step completes 4.5 blocks on average -- one trip instead of two).  The flushing lanes are ranked (mbcnt); two wave permutes hand lane j the id and the block number of the j-th
-            // flushing lane, and per trip a group of 16 lanes fetches "its" pair with two more permutes -- no scalar loop over the vote.
             if (m_flush) {
                 const bool flush = IBAL(m_flush);
-                const uint32_t nfl = (uint32_t)__builtin_popcountll(m_flush);
-                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_flush >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_flush, 0u));
-                const uint32_t dst = (flush ? rk : nfl + lane - rk) << 2;                // a full permutation: flushing lanes first, in lane order
-                const uint32_t ent_l = (uint32_t)__builtin_amdgcn_ds_permute((int)dst, (int)lane);
-                const uint32_t ent_b = (uint32_t)__builtin_amdgcn_ds_permute((int)dst, (int)fblk);
-                for (uint32_t t0 = 0; t0 < nfl; t0 += 8u) {
-                    const uint32_t idx = t0 + (lane >> 3);
-                    const uint32_t src = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)ent_l);
-                    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)ent_b);
-                    if (idx < nfl) {
-                        uint4* sb = reinterpret_cast<uint4*>(s_blk[wave0 + src]) + (lane & 7u);
-                        const uint4 v = *sb;
-                        *sb = make_uint4(0u, 0u, 0u, 0u);
-                        // (written once, read once by a later kernel, 6.4 GB per 1024 images: kept out of the caches' way -- 3.42 -> 3.31 ms)
-                        { typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4))); u32x4_nt t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-                          __builtin_nontemporal_store(t, reinterpret_cast<u32x4_nt*>(reinterpret_cast<char*>(cbase) + ((b << 7) | ((lane & 7u) << 4)))); }   // scalar base + 32-bit vector offset
+                // ---- the whole wave moves every block that completed in this step: 8 lanes x 16 bytes per block, eight blocks per store
+                // instruction (round 6; four per instruction before: 3.35 -> 3.23 ms, a step completes 4.5 blocks on average -- one trip instead of two).  The flushing lanes are ranked (mbcnt); two wave permutes hand lane j the id and the block number of the j-th
+                // flushing lane, and per trip a group of 16 lanes fetches "its" pair with two more permutes -- no scalar loop over the vote.
+                if constexpr (!DC) {
+                    const uint32_t nfl = (uint32_t)__builtin_popcountll(m_flush);
+                    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_flush >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_flush, 0u));
+                    const uint32_t dst = (flush ? rk : nfl + lane - rk) << 2;                // a full permutation: flushing lanes first, in lane order
+                    const uint32_t ent_l = (uint32_t)__builtin_amdgcn_ds_permute((int)dst, (int)lane);
+                    const uint32_t ent_b = (uint32_t)__builtin_amdgcn_ds_permute((int)dst, (int)fblk);
+                    for (uint32_t t0 = 0; t0 < nfl; t0 += 8u) {
+                        const uint32_t idx = t0 + (lane >> 3);
+                        const uint32_t src = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)ent_l);
+                        const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)ent_b);
+                        if (idx < nfl) {
+                            uint4* sb = reinterpret_cast<uint4*>(s_blk[wave0 + src]) + (lane & 7u);
+                            const uint4 v = *sb;
+                            *sb = make_uint4(0u, 0u, 0u, 0u);
+                            // (written once, read once by a later kernel, 6.4 GB per 1024 images: kept out of the caches' way -- 3.42 -> 3.31 ms)
+                            { typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4))); u32x4_nt t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+                              __builtin_nontemporal_store(t, reinterpret_cast<u32x4_nt*>(reinterpret_cast<char*>(cbase) + ((b << 7) | ((lane & 7u) << 4)))); }   // scalar base + 32-bit vector offset
+                        }
                     }
                 }
+                // ---- the DC difference joins the lane's queue; a lane that holds eight stores them
                 if (flush) {
-                    dcq0 = __builtin_amdgcn_alignbit(dcq1, dcq0, 16u); dcq1 = __builtin_amdgcn_alignbit(dcq2, dcq1, 16u); dcq2 = __builtin_amdgcn_alignbit(dcq3, dcq2, 16u);
-                    dcq3 = (dcq3 >> 16) | (dq0 << 16); dccnt++; dclast = fblk;
-                }
-                if (WBALLOT(dccnt >= 8u)) {
-                    if (dccnt >= 8u) {
-                        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                        u32x4_t t; t.x = dcq0; t.y = dcq1; t.z = dcq2; t.w = dcq3;
-                        *reinterpret_cast<u32x4_t*>(dbase + (dclast - 7u)) = t;
-                        dccnt = 0;
-                    }
-                }
-            }
-        }
-    }
-    dc_store_rest();
-    if (verify) {
-        if (check_n && !IBAL(m_cap) && res_p != P_END) { res_p = cur.p; res_s = cur.p == P_END ? 0u : ST_MAKE(seg, c, k); res_n = nblk; }
-        // the chain must be at its fixed point, and the block count that fed the prefix sum must be the real one
-        const uint32_t want_p = HALF && !hi ? half_p[g] : A.out_p[g], want_s = HALF && !hi ? half_s[g] : A.out_s[g];
-        const uint32_t want_n = HALF ? (hi ? A.nblk[g] - half_n[g] : half_n[g]) : A.nblk[g];
-        if (res_p != want_p || res_s != want_s || (check_n && res_n != want_n)) fl |= F_NOSYNC;
-    }
-    if (fl) { FLAG_OR(flags, img, fl); if (an != 0xFFFFFFFFu) ANOM_MIN(flags, img, an); }
-    if (REC) {
-        __syncthreads();
-        uint32_t* ho = side + im.side_off + JS_SIDE_HISTO;
-        for (uint32_t q = threadIdx.x; q < 2 * 4 * 17; q += SY_THREADS) { const uint32_t v = s_histo[q]; if (v) atomicAdd(&ho[q], v); }
-    }
-}
-
-// WRITE pass of the DC-only fast form (every image of the launch has decode_ac == 0 and goes on to k_dc_color): the walk of k_write2 --
-// same entry states, same steps, same walk_slow at interval ends, same verification, flags, anomaly keys and restart marks, word for
-// word -- without anything that serves the coefficient arena: no lane-private block in LDS, no de-zigzag store, no flush.  What a block
-// leaves is its dequantised DC difference, queued eight per lane into dccum exactly as there.  LDS holds the decode tables only, so a
-// CU takes as many workgroups as its wave slots allow.  One lane per sub-sequence always (the middle states of the candidate chain are
-// an accelerator, not part of the result).
-template <int WL>
-__global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
-                                                         const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
-                                                         const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
-                                                         int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
-                                                         uint32_t tab_rows, uint32_t tab_lut2)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-    const uint32_t wg = blockIdx.x + sy_base[0];
-    const uint32_t img = find_image(sy_base, nimg, wg);
-    const JsImage& im = imgs[img];
-    if (!tables[im.tableset].lut_ok) return;
-    const uint32_t* sd = side + im.side_off;
-    const uint32_t total_bits = sd[10] * 8, nseg = min(sd[11], im.seg_cap - 1);
-    const uint32_t sub0 = (wg - sy_base[img]) * SY_THREADS, i = sub0 + threadIdx.x;
-    if (sub0 * SUB_BITS >= total_bits) return;
-    if (im.total_blocks >= (1u << 25)) { if (threadIdx.x == 0) { FLAG_OR(flags, img, F_SHORT); ANOM_MIN(flags, img, ANOM_KEY(0u, AK_MIRROR)); } return; }   // (as k_write2: the exact kernel's)
-    const JsTableSet& tset = tables[im.tableset];
-    SubTabs T; T.nb = im.blk_per_mcu; T.n1 = im.samp_h[1] * im.samp_v[1]; T.n2 = im.ncomp == 3 ? T.n1 + im.samp_h[2] * im.samp_v[2] : T.nb;
-    WriteTabs W; load_wtabs(W, s_dyn, tset, tab_rows, tab_lut2, im.ncomp, threadIdx.x, SY_THREADS);
-    __syncthreads();
-
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(ustr + im.ustr_off);
-    const uint32_t* st = seg_tab + im.seg_off;
-    int16_t* dbase = dccum + im.coef_off; uint8_t* rstf = mcu_rst + im.mcu_off;
-    const uint32_t nblocks = im.total_blocks, prec_shift = im.precision >= 8 ? ((im.precision - 8) & 31) : 0;
-    const bool in_data = i * SUB_BITS < total_bits;
-    const size_t g = im.subseq_off + i;
-    uint32_t fl = 0, an = 0xFFFFFFFFu, nblk = 0, seg = 0, c = 0, k = 0, seg_end = 0, blk = 0;
-    uint32_t res_p = 0, res_s = 0, res_n = 0;                // what this lane reports for verification
-    bool verify = false, check_n = false, active0 = false, skip0 = false;
-    const uint32_t own_end = min((i + 1) * SUB_BITS, total_bits);
-    Cursor cur; cur.words = words; cur.widx = 0; cur.poff = 0; cur.w0 = cur.w1 = cur.nxt = 0; cur.sh = 0; cur.p = 0;
-    if (in_data) {
-        const uint32_t p0 = i ? A.out_p[g - 1] : 0u, s0 = i ? A.out_s[g - 1] : 0u;
-        blk = A.base[g]; seg = ST_SEG(s0); c = ST_C(s0); k = ST_K(s0);
-        verify = true;
-        if (p0 != P_END && p0 >= own_end) { res_p = p0; res_s = s0; }                          // owns no symbol: passes through
-        else if (p0 == P_END || (p0 >= total_bits && seg + 1 >= nseg)) { res_p = P_END; res_s = 0; check_n = true; }
-        else if (blk >= nblocks) verify = false;                                                // everything owned lies past the last MCU
-        else { active0 = true; check_n = true; seg_end = st[seg + 1] * 8; skip0 = k != 0; cur_init<WL>(cur, words, p0); }
-    }
-    const uint32_t wb0 = W.wb0, wb1 = W.wb1, wb2 = W.wb2;       // per component: byte offset of its DC row | of its AC row << 16
-    const char* l1b = W.rows;
-    const uint32_t qd0 = W.qz[0] & 0xFFFFu, qd1 = W.qz[64] & 0xFFFFu, qd2 = W.qz[128] & 0xFFFFu;     // the three DC quantisers
-    uint32_t comp = comp_of(T, c), wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
-    uint64_t m_act = WBALLOT(active0), m_skip = WBALLOT(skip0), m_cap = 0ull;
-    uint32_t dcq0 = 0, dcq1 = 0, dcq2 = 0, dcq3 = 0, dccnt = 0, dclast = 0, dq0 = 0;      // the DC queue of k_write2
-    uint32_t rst_blk = 0xFFFFFFFFu;
-    for (;;) {
-        // ---- end of the owned range
-        const uint64_t m_end = WBALLOT(cur.p >= own_end) & m_act;
-        if (m_end) {
-            if (IBAL(m_end & ~m_cap)) { res_p = cur.p; res_s = ST_MAKE(seg, c, k); res_n = nblk; }
-            m_cap |= m_end;
-            m_act &= ~(m_end & (WBALLOT(k == 0) | m_skip));
-        }
-        if (!m_act) break;
-        // ---- table entry
-        const uint32_t win = cur_peek(cur);
-        const uint32_t widx = win >> (32 - JS_L1_BITS);
-        const uint64_t m_dc = WBALLOT(k == 0);
-        const uint32_t e_dc = (uint32_t)(int32_t)*reinterpret_cast<const int16_t*>(l1b + ((wb & 0xFFFFu) + (widx << 1)));
-        const uint32_t e_ac = *reinterpret_cast<const uint32_t*>(l1b + ((wb >> 16) + (widx << 2)));
-        uint32_t e = IBAL(m_dc) ? e_dc : e_ac;
-        uint32_t len = e & 15u, size = (e >> 4) & 15u, run = (e >> 8) & 15u;
-        const uint64_t m_esc = WBALLOT((int32_t)e < 0) & m_act;
-        if (m_esc) {
-            if (IBAL(m_esc)) {
-                const uint32_t nbx = (e >> 12) & 7u;
-                const uint32_t e2 = W.lut2[(e & 0xFFFu) + __builtin_amdgcn_ubfe(win, 32u - JS_L1_BITS - nbx, nbx)];
-                const bool nocode = e == 0xC0000000u;
-                len = nocode ? 0u : (e2 >> 8) & 31u; run = nocode ? 0u : (e2 >> 4) & 15u; size = nocode ? 0u : e2 & 15u;
-                e = 1u << 24;
-            }
-        }
-        uint32_t tot = len + size;
-        uint32_t k2 = k + run + 1u;
-        // ---- the symbol behind it, from a table read of its own (as k_write2)
-        const uint32_t win2 = win << tot;
-        const uint32_t e_b = *reinterpret_cast<const uint32_t*>(l1b + ((wb >> 16) + ((win2 >> (32 - JS_L1_BITS)) << 2)));
-        if ((e >> 12) == 0u && (int32_t)e_b >= 0 && (IBAL(m_dc) || (e & 0xFF0u) != 0u)) e |= (e_b & 0xFFFu) << 12;
-        const uint32_t len2 = (e >> 12) & 15u, size2 = (e >> 16) & 15u, run2 = (e >> 20) & 15u, tot2 = len2 + size2, k3 = k2 + run2 + 1u;
-        const uint32_t p1 = cur.p + tot, p2 = p1 + tot2;
-        uint64_t m_two = WBALLOT(tot2 != 0u) & WBALLOT(k3 <= 64u) & WBALLOT(p1 < own_end) & WBALLOT(p2 <= seg_end) & WBALLOT(tot + tot2 <= JS_STEP_BITS) & m_act;
-        // ---- anything out of the ordinary, behind one vote
-        uint64_t m_norm = m_act, m_bad = 0ull;
-        const uint64_t m_abn = (WBALLOT(len == 0u) | WBALLOT(p1 > seg_end) | WBALLOT(k2 > 64u)) & m_act;
-        if (m_abn) {
-            const uint64_t m_slow = (WBALLOT(len == 0u) | WBALLOT(cur.p + len > seg_end)) & m_act;
-            bool over = false, bad = false;
-            if (IBAL(m_slow)) {
-                const bool notcap = !IBAL(m_cap);
-                const uint32_t seg_was = seg;
-                const int ws = walk_slow<true, WL>(im, words, st, nseg, cur, len, seg, seg_end, c, k, blk, notcap, rstf, fl, an);
-                rst_blk = seg != seg_was ? blk : rst_blk;
-                if (ws == WS_OVER && notcap) { res_p = P_END; res_s = 0; res_n = nblk; }
-                over = ws == WS_OVER; bad = ws == WS_BAD_CODE;
-                comp = comp_of(T, c); wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
-                tot = 0; size = 0; k2 = k;
-            } else if (IBAL(m_act)) {
-                if (blk < nblocks) {
-                    if (p1 > seg_end) { fl |= F_OVERRUN; an = min(an, ANOM_KEY(blk, seg + 1u < nseg ? AK_DEAD + (IBAL(m_dc) ? 0u : 1u) + (rst_blk == blk ? 2u : 0u) + (IBAL(m_skip) ? 4u : 0u) : AK_MIRROR)); }
-                    if (k2 > 64u) fl |= F_COEF_OVERFLOW;
-                }
-            }
-            const uint64_t m_over = WBALLOT(over);
-            m_bad = WBALLOT(bad) & m_act;
-            m_cap |= m_over; m_act &= ~m_over;
-            m_norm &= ~m_slow; m_two &= ~m_slow;
-        }
-        // ---- the DC difference: EXTEND, precision divide, dequantise (AC values are parsed, not formed)
-        int32_t val = extend_bits(win, len, size);
-        if (prec_shift) val /= (int32_t)(1u << prec_shift);
-        const uint32_t qd = comp == 0 ? qd0 : (comp == 1 ? qd1 : qd2);
-        dq0 = IBAL(m_dc & m_norm) ? (uint32_t)((int32_t)(int16_t)val * (int32_t)qd) : dq0;
-        if (m_bad) { if (IBAL(m_bad & m_dc)) dq0 = 0u; }          // a code that matches nothing in front of the DC value: the block keeps a zero difference
-        // ---- advance
-        const bool two = IBAL(m_two);
-        { const uint32_t adv = tot + (two ? tot2 : 0u); cur.sh -= (int32_t)adv; cur.p += adv; }
-        if (IBAL(WBALLOT(cur.sh < 0) & m_act)) {
-            cur.sh += 32; cur.w0 = cur.w1; cur.w1 = bswap32(cur.nxt);
-            cur.nxt = cur_fetch<WL>(cur);
-        }
-        const uint32_t kn = two ? k3 : k2;
-        const uint64_t m_eob = (m_two & WBALLOT((run2 | size2) == 0u)) | (~m_two & WBALLOT((run | size) == 0u));
-        const uint64_t m_done = (m_norm & (~m_dc | m_two) & (m_eob | WBALLOT(kn >= 64u))) | m_bad;   // (a DC symbol ends no block; the AC symbol that went along with it may)
-        k = IBAL(m_done) ? 0u : kn;
-        if (m_done) {
-            const uint64_t m_flush = m_done & ~m_skip & WBALLOT(blk < nblocks);
-            const uint32_t fblk = blk;
-            if (IBAL(m_done)) {
-                c = c + 1 == T.nb ? 0u : c + 1; comp = comp_of(T, c); wb = comp == 0 ? wb0 : (comp == 1 ? wb1 : wb2);
-                nblk += IBAL(m_cap) ? 0u : 1u;
-                blk++;
-            }
-            m_skip &= ~m_done;
-            if (m_flush) {
-                if (IBAL(m_flush)) {
                     dcq0 = __builtin_amdgcn_alignbit(dcq1, dcq0, 16u); dcq1 = __builtin_amdgcn_alignbit(dcq2, dcq1, 16u); dcq2 = __builtin_amdgcn_alignbit(dcq3, dcq2, 16u);
                     dcq3 = (dcq3 >> 16) | (dq0 << 16); dccnt++; dclast = fblk;
                 }
@@ -3581,11 +3427,37 @@ __global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restri
         const uint32_t q = h < 2 ? dcq0 : (h < 4 ? dcq1 : (h < 6 ? dcq2 : dcq3));
         if (h + dccnt >= 8u) dbase[dclast - 7u + h] = (int16_t)((h & 1u) ? q >> 16 : q);
     }
-    if (verify) {
-        if (check_n && !IBAL(m_cap) && res_p != P_END) { res_p = cur.p; res_s = cur.p == P_END ? 0u : ST_MAKE(seg, c, k); res_n = nblk; }
-        if (res_p != A.out_p[g] || res_s != A.out_s[g] || (check_n && res_n != A.nblk[g])) fl |= F_NOSYNC;
+    if (E.verify) {
+        const uint32_t want_p = HALF && !hi ? half_p[g] : A.out_p[g], want_s = HALF && !hi ? half_s[g] : A.out_s[g];
+        const uint32_t want_n = !E.check_n ? 0u : (HALF ? (hi ? A.nblk[g] - half_n[g] : half_n[g]) : A.nblk[g]);
+        fl |= walk_verify(E.check_n, IBAL(m_cap), res_p, res_s, res_n, cur.p, ST_MAKE(seg, c, k), nblk, want_p, want_s, want_n);
     }
     if (fl) { FLAG_OR(flags, img, fl); if (an != 0xFFFFFFFFu) ANOM_MIN(flags, img, an); }
+    if (REC) histo_spill(s_histo, side + im.side_off + JS_SIDE_HISTO);
+}
+template <int WL, bool HALF = false, bool REC = false>
+__global__ void __launch_bounds__(SY_THREADS) k_write2(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
+                                                       const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
+                                                       const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
+                                                       int16_t* __restrict__ coef, int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
+                                                       uint32_t tab_rows, uint32_t tab_lut2, const uint32_t* __restrict__ half_p = nullptr, const uint32_t* __restrict__ half_s = nullptr,
+                                                       const uint32_t* __restrict__ half_n = nullptr, uint32_t* __restrict__ rec_pos = nullptr)
+{
+    __shared__ __attribute__((aligned(16))) int16_t s_blk[SY_THREADS][WR_STRIDE];
+    __shared__ uint32_t s_histo[REC ? 2 * 4 * 17 : 1];
+    write_walk<WL, HALF, REC, false>(s_blk, s_histo, imgs, sy_base, nimg, tables, ustr, seg_tab, side, A, coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, half_p, half_s, half_n, rec_pos);
+}
+// WRITE pass of the DC-only fast form: the same walk without the coefficient arena.  LDS holds the decode tables only, so a CU takes as
+// many workgroups as its wave slots allow.  One lane per sub-sequence always (the middle states of the candidate chain are an accelerator,
+// not part of the result).
+template <int WL>
+__global__ void __launch_bounds__(SY_THREADS) k_write_dc(const JsImage* __restrict__ imgs, const uint32_t* __restrict__ sy_base, uint32_t nimg,
+                                                         const JsTableSet* __restrict__ tables, const uint8_t* __restrict__ ustr,
+                                                         const uint32_t* __restrict__ seg_tab, uint32_t* __restrict__ side, SubArrays A,
+                                                         int16_t* __restrict__ dccum, uint8_t* __restrict__ mcu_rst, uint32_t* __restrict__ flags,
+                                                         uint32_t tab_rows, uint32_t tab_lut2)
+{
+    write_walk<WL, false, false, true>(nullptr, nullptr, imgs, sy_base, nimg, tables, ustr, seg_tab, side, A, nullptr, dccum, mcu_rst, flags, tab_rows, tab_lut2, nullptr, nullptr, nullptr, nullptr);
 }
 
 // One workgroup (1024 lanes) per image: DC differences (in dccum, decode order) -> cumulative DC per block.
@@ -3713,6 +3585,13 @@ void js_launch_unstuff(hipStream_t st, int wl, const JsImage* imgs, const uint32
     else if (wl == 7) hipLaunchKernelGGL(k_interleave<7>, dim3(sy_wgs * 4), dim3(256), 0, st, imgs, sy_base, nimg, side, ustr_lin, ustr);
     else hipLaunchKernelGGL(k_interleave<5>, dim3(sy_wgs * 4), dim3(256), 0, st, imgs, sy_base, nimg, side, ustr_lin, ustr);
 }
+// One launch of a kernel that is a template of the sub-sequence width: K spells the instance with W for the width, in parentheses --
+// JS_LAUNCH_WL((k_write<W, true>), grid, block, lds, arguments...) -- and goes to the stream `st` for the caller's `wl` (4..8, the host admits nothing else; anything else would take <5>).
+#define JS_LAUNCH_W(N, K, ...) { constexpr int W = N; hipLaunchKernelGGL(K, __VA_ARGS__); }
+#define JS_LAUNCH_WL(K, GRID, BLOCK, LDS, ...) \
+    do { if (wl == 4) JS_LAUNCH_W(4, K, GRID, BLOCK, LDS, st, __VA_ARGS__) else if (wl == 6) JS_LAUNCH_W(6, K, GRID, BLOCK, LDS, st, __VA_ARGS__) \
+         else if (wl == 7) JS_LAUNCH_W(7, K, GRID, BLOCK, LDS, st, __VA_ARGS__) else if (wl == 8) JS_LAUNCH_W(8, K, GRID, BLOCK, LDS, st, __VA_ARGS__) \
+         else JS_LAUNCH_W(5, K, GRID, BLOCK, LDS, st, __VA_ARGS__) } while (0)
 static SubArrays sub_arrays(uint32_t* sub, uint64_t n) { SubArrays a; a.out_p = sub; a.out_s = sub + n; a.in_p = sub + 2 * n; a.in_s = sub + 3 * n; a.nblk = sub + 4 * n; a.base = sub + 5 * n; return a; }
 static size_t subtabs_bytes_host(uint32_t tab_rows, uint32_t tab_lut2, bool pairs = false)
 { return pairs ? (size_t)tab_rows * (4u << JS_L1_BITS) + (size_t)tab_lut2 * 4 : (size_t)tab_rows * (2u << JS_L1_BITS) + (((size_t)tab_lut2 * 2 + 15) & ~15ull) + 3 * 64 * 4; }   // (load_subtabs)
@@ -3720,16 +3599,8 @@ void js_launch_sync(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2
                     const uint8_t* ustr, const uint32_t* seg_tab, const uint32_t* side, uint32_t* sub, uint64_t nsub, int first_pass, uint32_t it_max)
 {
     if (!total_wgs) return;
-    if (wl == 4) hipLaunchKernelGGL(k_sync<4>, dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
-    else if (wl == 6) hipLaunchKernelGGL(k_sync<6>, dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
-    else if (wl == 8) hipLaunchKernelGGL(k_sync<8>, dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
-    else if (wl == 7) hipLaunchKernelGGL(k_sync<7>, dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
-    else hipLaunchKernelGGL(k_sync<5>, dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
+    JS_LAUNCH_WL((k_sync<W>), dim3(total_wgs), dim3(SY_THREADS), subtabs_bytes_host(tab_rows, tab_lut2, true), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                 sub_arrays(sub, nsub), first_pass, tab_rows, tab_lut2, it_max);
 }
 size_t js_sync_list_words(uint64_t nsub, uint32_t nimg) { return (size_t)2 * nsub + (size_t)nimg * SYR_SLOTS; }
 // The large-job form: first launch of k_sync cut after its second round, then `rounds` list rounds (<= SYR_SLOTS - 1) and the verification mode.
@@ -3746,14 +3617,9 @@ void js_launch_sync_rounds(hipStream_t st, int wl, uint32_t tab_rows, uint32_t t
     const SubArrays A = sub_arrays(sub, nsub);
     const size_t lds = subtabs_bytes_host(tab_rows, tab_lut2, true);
     uint32_t* l0 = lists; uint32_t* l1 = lists + nsub;
-#define SYR_WL(K, GRID, BLOCK, LDS, ...) \
-    do { if (wl == 4) hipLaunchKernelGGL(K<4>, GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 5) hipLaunchKernelGGL(K<5>, GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else if (wl == 6) hipLaunchKernelGGL(K<6>, GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 7) hipLaunchKernelGGL(K<7>, GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else hipLaunchKernelGGL(K<8>, GRID, BLOCK, LDS, st, __VA_ARGS__); } while (0)
-    SYR_WL(k_sync_links, dim3(sy_wgs), dim3(256), 0, imgs, sy_base, nimg, tables, side, A, l0, rcnt);
+    JS_LAUNCH_WL((k_sync_links<W>), dim3(sy_wgs), dim3(256), 0, imgs, sy_base, nimg, tables, side, A, l0, rcnt);
     for (int r = 0; r < rounds; r++)
-        SYR_WL(k_sync_round, dim3(sy_wgs), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, A, (const uint32_t*)((r & 1) ? l1 : l0), (r & 1) ? l0 : l1, rcnt, (uint32_t)r, tab_rows, tab_lut2);
-#undef SYR_WL
+        JS_LAUNCH_WL((k_sync_round<W>), dim3(sy_wgs), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, A, (const uint32_t*)((r & 1) ? l1 : l0), (r & 1) ? l0 : l1, rcnt, (uint32_t)r, tab_rows, tab_lut2);
     js_launch_sync(st, wl, tab_rows, tab_lut2, imgs, sn_base, nimg, sn_wgs, tables, ustr, seg_tab, side, sub, nsub, 2, 0u);
 }
 // ---- candidate synchronisation (small jobs).  cand: js_cand_bytes(nsub) bytes; req: nimg * JS_CAND_REQ_WORDS words
@@ -3769,14 +3635,6 @@ static CandArrays cand_arrays(uint32_t* c, uint64_t n)
 size_t js_cand_bytes(uint64_t nsub) { return (size_t)nsub * ((2 * CD_H + 8 * CD_SLOTS + 5) * 4 + 2) + 8192; }   // (slack: the chain reads whole 512-map tiles)
 static_assert(CD_DIAG_WORDS == JS_CAND_REQ_WORDS, "diagnostics area size");
 static_assert(CD_H == JS_CAND_MAX_BLK, "hypotheses");
-#define CAND_WL(K, GRID, BLOCK, LDS, ...) \
-    do { if (wl == 4) hipLaunchKernelGGL(K<4>, GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 5) hipLaunchKernelGGL(K<5>, GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else if (wl == 6) hipLaunchKernelGGL(K<6>, GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 7) hipLaunchKernelGGL(K<7>, GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else hipLaunchKernelGGL(K<8>, GRID, BLOCK, LDS, st, __VA_ARGS__); } while (0)
-#define CAND_WL2(K, GRID, BLOCK, LDS, ...) \
-    do { if (wl == 4) hipLaunchKernelGGL((K<4, false>), GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 5) hipLaunchKernelGGL((K<5, false>), GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else if (wl == 6) hipLaunchKernelGGL((K<6, false>), GRID, BLOCK, LDS, st, __VA_ARGS__); else if (wl == 7) hipLaunchKernelGGL((K<7, false>), GRID, BLOCK, LDS, st, __VA_ARGS__); \
-         else hipLaunchKernelGGL((K<8, false>), GRID, BLOCK, LDS, st, __VA_ARGS__); } while (0)
 void js_launch_cand_sync(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* sy_base, uint32_t nimg, uint32_t sy_wgs, uint32_t max_blk,
                          const JsTableSet* tables, const uint8_t* ustr, const uint32_t* seg_tab, const uint32_t* side, uint32_t* sub, uint64_t nsub, uint32_t* cand, uint32_t* req, int fill_rounds,
                          int mid /* the memo walks report the state at the middle of every sub-sequence too (64-byte pieces only): the write pass will run two lanes per sub-sequence */)
@@ -3784,31 +3642,22 @@ void js_launch_cand_sync(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab
     if (!sy_wgs || !nimg) return;
     const size_t lds = subtabs_bytes_host(tab_rows, tab_lut2, true);
     const CandArrays C = cand_arrays(cand, nsub);
-    CAND_WL(k_cand_spec, dim3(sy_wgs, max_blk), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, C, tab_rows, tab_lut2);
+    JS_LAUNCH_WL((k_cand_spec<W>), dim3(sy_wgs, max_blk), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, C, tab_rows, tab_lut2);
     if (mid && wl == 4) {
         hipLaunchKernelGGL((k_cand_walk<4, true>), dim3(sy_wgs, CD_H), dim3(SY_THREADS), lds, st, imgs, sy_base, nimg, tables, ustr, seg_tab, side, C, tab_rows, tab_lut2);
         hipLaunchKernelGGL((k_cand_chain<4, true>), dim3(nimg), dim3(CC_THREADS), lds, st, imgs, tables, ustr, seg_tab, side, C, req, fill_rounds, tab_rows, tab_lut2);
     } else {
         mid = 0;
-        CAND_WL2(k_cand_walk, dim3(sy_wgs, CD_H), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, C, tab_rows, tab_lut2);
-        CAND_WL2(k_cand_chain, dim3(nimg), dim3(CC_THREADS), lds, imgs, tables, ustr, seg_tab, side, C, req, fill_rounds, tab_rows, tab_lut2);
+        JS_LAUNCH_WL((k_cand_walk<W, false>), dim3(sy_wgs, CD_H), dim3(SY_THREADS), lds, imgs, sy_base, nimg, tables, ustr, seg_tab, side, C, tab_rows, tab_lut2);
+        JS_LAUNCH_WL((k_cand_chain<W, false>), dim3(nimg), dim3(CC_THREADS), lds, imgs, tables, ustr, seg_tab, side, C, req, fill_rounds, tab_rows, tab_lut2);
     }
-    CAND_WL(k_cand_apply, dim3(sy_wgs), dim3(SY_THREADS), 0, imgs, sy_base, nimg, tables, side, C, sub_arrays(sub, nsub), mid);
+    JS_LAUNCH_WL((k_cand_apply<W>), dim3(sy_wgs), dim3(SY_THREADS), 0, imgs, sy_base, nimg, tables, side, C, sub_arrays(sub, nsub), mid);
 }
 void js_launch_block_scan(hipStream_t st, int wl, const JsImage* imgs, uint32_t nimg, const JsTableSet* tables, uint32_t* sub, uint64_t nsub, uint32_t* side, uint32_t* flags)
 {
     if (!nimg) return;
-    if (nimg <= 8) {                                             // a few (large) images: wide workgroups, fewer serial steps
-        if (wl == 4) hipLaunchKernelGGL((k_block_scan<4, 1024>), dim3(nimg), dim3(1024), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 6) hipLaunchKernelGGL((k_block_scan<6, 1024>), dim3(nimg), dim3(1024), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 8) hipLaunchKernelGGL((k_block_scan<8, 1024>), dim3(nimg), dim3(1024), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 7) hipLaunchKernelGGL((k_block_scan<7, 1024>), dim3(nimg), dim3(1024), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-        else hipLaunchKernelGGL((k_block_scan<5, 1024>), dim3(nimg), dim3(1024), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    } else if (wl == 4) hipLaunchKernelGGL((k_block_scan<4, 256>), dim3(nimg), dim3(256), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 6) hipLaunchKernelGGL((k_block_scan<6, 256>), dim3(nimg), dim3(256), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 8) hipLaunchKernelGGL((k_block_scan<8, 256>), dim3(nimg), dim3(256), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else if (wl == 7) hipLaunchKernelGGL((k_block_scan<7, 256>), dim3(nimg), dim3(256), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
-    else hipLaunchKernelGGL((k_block_scan<5, 256>), dim3(nimg), dim3(256), 0, st, imgs, tables, sub_arrays(sub, nsub), side, flags);
+    if (nimg <= 8) JS_LAUNCH_WL((k_block_scan<W, 1024>), dim3(nimg), dim3(1024), 0, imgs, tables, sub_arrays(sub, nsub), side, flags);   // a few (large) images: wide workgroups, fewer serial steps
+    else JS_LAUNCH_WL((k_block_scan<W, 256>), dim3(nimg), dim3(256), 0, imgs, tables, sub_arrays(sub, nsub), side, flags);
 }
 void js_launch_write(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* sy_base, uint32_t nimg, uint32_t total_wgs, const JsTableSet* tables,
                      const uint8_t* ustr, const uint32_t* seg_tab, uint32_t* side, uint32_t* sub, uint64_t nsub,
@@ -3827,38 +3676,20 @@ void js_launch_write(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut
     if (!v1) {
         if (wl == 4 && rec_pos) hipLaunchKernelGGL((k_write2<4, false, true>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
                            sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, rec_pos);
-        else if (wl == 4) hipLaunchKernelGGL((k_write2<4>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                           sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
-    else if (wl == 6) hipLaunchKernelGGL((k_write2<6>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                           sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
-    else if (wl == 8) hipLaunchKernelGGL((k_write2<8>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                           sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
-    else if (wl == 7) hipLaunchKernelGGL((k_write2<7>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                           sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
-        else hipLaunchKernelGGL((k_write2<5>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                           sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
+        else JS_LAUNCH_WL((k_write2<W>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                          sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2);
         return;
     }
-    if (wl == 4) hipLaunchKernelGGL((k_write<4, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
-    else if (wl == 6) hipLaunchKernelGGL((k_write<6, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
-    else if (wl == 8) hipLaunchKernelGGL((k_write<8, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
-    else if (wl == 7) hipLaunchKernelGGL((k_write<7, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
-    else hipLaunchKernelGGL((k_write<5, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
+    JS_LAUNCH_WL((k_write<W, false>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                 sub_arrays(sub, nsub), coef, dccum, mcu_rst, flags, tab_rows, tab_lut2, 0u, (uint32_t*)nullptr);
 }
 // the write pass of the DC-only fast form (k_write_dc): no coefficient arena, one lane per sub-sequence
 void js_launch_write_dc(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab_lut2, const JsImage* imgs, const uint32_t* sy_base, uint32_t nimg, uint32_t total_wgs, const JsTableSet* tables,
                         const uint8_t* ustr, const uint32_t* seg_tab, uint32_t* side, uint32_t* sub, uint64_t nsub, int16_t* dccum, uint8_t* mcu_rst, uint32_t* flags)
 {
     if (!total_wgs) return;
-#define JS_WRITE_DC(W) hipLaunchKernelGGL((k_write_dc<W>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side, \
-                                          sub_arrays(sub, nsub), dccum, mcu_rst, flags, tab_rows, tab_lut2)
-    if (wl == 4) JS_WRITE_DC(4); else if (wl == 6) JS_WRITE_DC(6); else if (wl == 7) JS_WRITE_DC(7); else if (wl == 8) JS_WRITE_DC(8); else JS_WRITE_DC(5);
-#undef JS_WRITE_DC
+    JS_LAUNCH_WL((k_write_dc<W>), dim3(total_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                 sub_arrays(sub, nsub), dccum, mcu_rst, flags, tab_rows, tab_lut2);
 }
 // =====================================================================================
 //  Side outputs of an image the parallel path decoded, without the sequential kernel:
@@ -4252,10 +4083,8 @@ void js_launch_side_pass_all(hipStream_t st, int wl, uint32_t tab_rows, uint32_t
     hipLaunchKernelGGL(k_side_clear_all, dim3(16, nimg), dim3(256), 0, st, imgs, img_mask, side, events);
     hipLaunchKernelGGL(k_unstuff_write<false>, dim3(us_wgs), dim3(US_THREADS), 0, st, imgs, us_base, nimg, raw, const_cast<uint32_t*>(chunk_keep), const_cast<uint32_t*>(chunk_rst), (uint8_t*)nullptr, seg_tab, 0u, us_all,
                        (unsigned long long*)nullptr, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
-#define JS_ALL_WALK(W) hipLaunchKernelGGL((k_write<W, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side, \
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, (uint32_t*)nullptr, tab_rows, tab_lut2, 0u, pos_all, img_mask)
-    if (wl == 4) JS_ALL_WALK(4); else if (wl == 6) JS_ALL_WALK(6); else if (wl == 8) JS_ALL_WALK(8); else if (wl == 7) JS_ALL_WALK(7); else JS_ALL_WALK(5);
-#undef JS_ALL_WALK
+    JS_LAUNCH_WL((k_write<W, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                 sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, (uint32_t*)nullptr, tab_rows, tab_lut2, 0u, pos_all, img_mask);
     hipLaunchKernelGGL(k_side_maps, dim3(16, nimg), dim3(256), 0, st, imgs, 0u, tables, raw, seg_tab, dccum, mcu_rst, pos_all, us_all, 0u, side, events, (uint32_t*)nullptr, 0xFFFFFFFFu, 0xFFFFFFFFu,
                        img_mask, us_base);
 }
@@ -4268,16 +4097,8 @@ void js_launch_side_pass(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab
     hipLaunchKernelGGL(k_unstuff_write<false>, dim3(us_wgs), dim3(US_THREADS), 0, st, imgs, us_base, nimg, raw, const_cast<uint32_t*>(chunk_keep), const_cast<uint32_t*>(chunk_rst), (uint8_t*)nullptr, seg_tab, us_wg0, us_out,
                        (unsigned long long*)nullptr, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
     if (walked) {}                                                 // (the write pass of the decode recorded positions and histogram itself: k_write2<., ., true>)
-    else if (wl == 4) hipLaunchKernelGGL((k_write<4, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
-    else if (wl == 6) hipLaunchKernelGGL((k_write<6, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
-    else if (wl == 8) hipLaunchKernelGGL((k_write<8, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
-    else if (wl == 7) hipLaunchKernelGGL((k_write<7, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
-    else hipLaunchKernelGGL((k_write<5, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side,
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
+    else JS_LAUNCH_WL((k_write<W, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                      sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, anoms, tab_rows, tab_lut2, sy_wg0, mcu_pos);
     hipLaunchKernelGGL(k_side_maps, dim3(64), dim3(256), 0, st, imgs, img, tables, raw, seg_tab, dccum, mcu_rst, mcu_pos, us_out, us_wgs * US_THREADS, side, events, anoms, dead_blk, cut_mcu);
 }
 // Tail take-over for image `img` of a decoded batch (see ExactTail): the inverse byte map and the MCU bit positions through the first two
@@ -4290,10 +4111,8 @@ void js_launch_tail_pass(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab
     if (!us_wgs || !sy_wgs) return;
     hipLaunchKernelGGL(k_unstuff_write<false>, dim3(us_wgs), dim3(US_THREADS), 0, st, imgs, us_base, nimg, raw, const_cast<uint32_t*>(chunk_keep), const_cast<uint32_t*>(chunk_rst), (uint8_t*)nullptr, seg_tab, us_wg0, us_out,
                        (unsigned long long*)nullptr, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
-#define JS_TAIL_WALK(W) hipLaunchKernelGGL((k_write<W, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), st, imgs, sy_base, nimg, tables, ustr, seg_tab, side, \
-                       sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, (uint32_t*)nullptr, tab_rows, tab_lut2, sy_wg0, mcu_pos)
-    if (wl == 4) JS_TAIL_WALK(4); else if (wl == 6) JS_TAIL_WALK(6); else if (wl == 8) JS_TAIL_WALK(8); else if (wl == 7) JS_TAIL_WALK(7); else JS_TAIL_WALK(5);
-#undef JS_TAIL_WALK
+    JS_LAUNCH_WL((k_write<W, true>), dim3(sy_wgs), dim3(SY_THREADS), wtabs_bytes(tab_rows, tab_lut2), imgs, sy_base, nimg, tables, ustr, seg_tab, side,
+                 sub_arrays(sub, nsub), (int16_t*)nullptr, (int16_t*)nullptr, mcu_rst, (uint32_t*)nullptr, tab_rows, tab_lut2, sy_wg0, mcu_pos);
     ExactTail t; t.flags = flags; t.seg_tab = seg_tab; t.mcu_rst = mcu_rst; t.mcu_pos = mcu_pos; t.us_out = us_out; t.us_threads = us_wgs * US_THREADS;
     hipLaunchKernelGGL(k_entropy_exact, dim3(1), dim3(64), 0, st, imgs, sel1, 1u, tables, raw, coef, dccum, side, 0, (uint32_t*)nullptr, t);
 }
