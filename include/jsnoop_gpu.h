@@ -380,6 +380,45 @@ int          jsnoop_batch_pack(JsnoopBatch*, const JsnoopPackSpec* spec, const i
 /* the device the batch lives on (jsnoop_set_device when it was created): where the destinations of jsnoop_batch_pack must be; -1 for NULL */
 int          jsnoop_batch_device(const JsnoopBatch*);
 
+/* ---- pack, cropped and resampled: a rectangle of every listed image at the size its destination asks for ------------------------------
+ * jsnoop_batch_pack_resized is jsnoop_batch_pack with a source rectangle (ROI) and an output size per destination: layout, dtype, bgr,
+ * scale and bias come from the same JsnoopPackSpec, pitches mean the same for an out_w x out_h image, and ONE kernel launch serves the
+ * whole list -- 1024 crops into one [N,3,H,W] allocation, or a set of differently sized thumbnails.  `images` may name an image several
+ * times (several crops of one file).  The ROI is given in the coordinates of the plain pack's output (top-down, cropped to dim_x x
+ * dim_y); roi_w == roi_h == 0 with roi_x == roi_y == 0 is the whole image.
+ *
+ * What a pixel is.  R is the ROI as a top-down rh x rw x 3 array of the DIB's bytes (the plain pack, cropped).  Output pixel (ox, oy),
+ * channel c, has the interpolant q = (float)((double)S / (double)D) with exact integers S and D (S < 2^53): one IEEE double division, one
+ * rounding to float; nothing outside the ROI contributes.
+ *   JSNOOP_RESIZE_NEAREST : x = ((2 ox + 1) rw) div (2 out_w), y likewise; S = R[y][x][c], D = 1.
+ *   JSNOOP_RESIZE_BILINEAR: half-pixel centres, edge replication inside the ROI (torch's bilinear, align_corners=False, no antialias):
+ *       Dx = 2 out_w, P = (2 ox + 1) rw - out_w; P < 0: x0 = 0, rx = 0; else x0 = P div Dx, rx = P mod Dx; x1 = min(x0 + 1, rw - 1);
+ *       likewise Dy, y0, y1, ry;  S = (Dx-rx)(Dy-ry) R[y0][x0] + rx (Dy-ry) R[y0][x1] + (Dx-rx) ry R[y1][x0] + rx ry R[y1][x1], D = Dx Dy.
+ *   JSNOOP_RESIZE_AREA    : box filter with fractional coverage.  In units of 1 / out_w source pixel output column ox covers
+ *       [ox rw, (ox+1) rw) and source column j covers [j out_w, (j+1) out_w); wx(ox, j) is the length of their overlap, wy likewise;
+ *       S = sum_j sum_i wy wx R[j][i][c], D = rw rh.
+ *   JSNOOP_PACK_U8 : q rounded to nearest, ties to even.   JSNOOP_PACK_F32: q * scale[c] + bias[c], one rounded multiply, one rounded add.
+ * With out_w == rw and out_h == rh every filter gives exactly the plain pack of the ROI.
+ *
+ * Ordering: jsnoop_batch_pack's -- enqueued on the batch's stream behind the decode enqueued last (both halves of a two-stream decode
+ * included), not waited for; a call before jsnoop_batch_sync sees what the parallel path left; never decodes again
+ * (jsnoop_batch_last_form is unchanged).
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: everything jsnoop_batch_pack refuses ("dense" meaning the
+ * output's out_w x out_h); an unknown filter; out_w or out_h of 0 or above 32767; an ROI with one of roi_w / roi_h zero and the other
+ * not, or with both zero and roi_x or roi_y not; an ROI that leaves dim_x x dim_y.  n == 0 is 0.                                     */
+#define JSNOOP_RESIZE_NEAREST  0
+#define JSNOOP_RESIZE_BILINEAR 1
+#define JSNOOP_RESIZE_AREA     2
+typedef struct JsnoopResizeDst {
+    void*    ptr; uint64_t row_pitch, plane_pitch;   /* as JsnoopPackDst, for an out_w x out_h image; 0 = dense */
+    uint32_t out_w, out_h;                           /* 1 .. 32767 each */
+    uint32_t roi_x, roi_y, roi_w, roi_h;             /* source rectangle in the coordinates of the plain pack's output (top-down, cropped
+                                                        to dim_x x dim_y); roi_w == roi_h == 0 (then roi_x == roi_y == 0) = the whole image */
+} JsnoopResizeDst;
+int          jsnoop_batch_pack_resized(JsnoopBatch*, const JsnoopPackSpec* spec, int filter,
+                                       const int* images, int n, const JsnoopResizeDst* dst);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

@@ -60,6 +60,16 @@ class PackDst(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64)]
 
 
+RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_AREA = 0, 1, 2
+
+
+class ResizeDst(C.Structure):
+    """JsnoopResizeDst of include/jsnoop_gpu.h: one destination of jsnoop_batch_pack_resized -- pointer and pitches as PackDst for an out_w x out_h
+    image, the output size (1 .. 32767 each) and the source rectangle in the plain pack's coordinates (roi_w == roi_h == 0: the whole image)."""
+    _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64), ("out_w", C.c_uint32), ("out_h", C.c_uint32),
+                ("roi_x", C.c_uint32), ("roi_y", C.c_uint32), ("roi_w", C.c_uint32), ("roi_h", C.c_uint32)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -183,6 +193,7 @@ SIGNATURES = {
     "jsnoop_pack_spec_defaults": (None, [C.POINTER(PackSpec)]),
     "jsnoop_batch_pack_bytes": (C.c_uint64, [_p, C.POINTER(PackSpec), _i]),
     "jsnoop_batch_pack": (_i, [_p, C.POINTER(PackSpec), _PI, _i, C.POINTER(PackDst)]),
+    "jsnoop_batch_pack_resized": (_i, [_p, C.POINTER(PackSpec), _i, _PI, _i, C.POINTER(ResizeDst)]),
     "jsnoop_batch_device": (_i, [_p]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),

@@ -255,6 +255,9 @@ public:
     // (jsnoop_batch_pack: enqueued on the batch's stream, not waited for; jsnoop_pack_spec_defaults fills a spec)
     bool     BatchPack(const JsnoopPackSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    // (jsnoop_batch_pack_resized: a rectangle of every listed file at its destination's size, filter = JSNOOP_RESIZE_*; same ordering)
+    bool     BatchPackResized(const JsnoopPackSpec& spec, int filter, const std::vector<int>& files, const std::vector<JsnoopResizeDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack_resized(m_b, &spec, filter, files.data(), (int)files.size(), dst.data()) == 0; }
     bool     BatchGetBitmap(int nFileInd, std::vector<uint8_t>& dib, unsigned& nX, unsigned& nY)
     {
         unsigned info[16]; if (jsnoop_batch_image_info(m_b, nFileInd, info)) return false;

@@ -126,6 +126,9 @@ struct JsnoopBatch {
     // ev_pack is recorded behind that copy and the next pack waits for it before it rewrites the block (the discipline of h_desc / ev_up)
     uint8_t* h_pack = nullptr; size_t h_pack_cap = 0; uint8_t* d_pack = nullptr; size_t d_pack_cap = 0; hipEvent_t ev_pack = nullptr;
     int  pack(const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);   // jsnoop_pack.cpp
+    int  pack_resized(const JsnoopPackSpec* spec, int filter, const int* images, int n, const JsnoopResizeDst* dst);   // jsnoop_pack.cpp; the same block and event
+    int  pack_block(size_t total);               // h_pack ready to be rewritten and at least `total` bytes large
+    int  pack_send(size_t total);                // h_pack -> d_pack on the batch stream, ev_pack behind the copy
     JsDeviceArenas dev; JsArenaCaps cap;
     bool uploaded;
     uint32_t us_ticket_base[2] = { 0, 0 };                        // value of the two chunk-ticket counters (behind us_state; one per part of a split decode) before the next launch

@@ -87,3 +87,7 @@ void js_launch_tail_pass(hipStream_t st, int wl, uint32_t tab_rows, uint32_t tab
 // recs / unit_base: JsPackRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error.
 int  js_launch_pack_rgb(hipStream_t st, const JsImage* imgs, const uint8_t* dib, const JsPackRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                         int layout /*JSNOOP_PACK_HWC / _CHW*/, int dtype /*JSNOOP_PACK_U8 / _F32*/, const JsPackArgs& a);
+// k_pack_resize (jsnoop_pack_resize.hip): a rectangle of every listed DIB resampled to its destination's size, ONE launch for the whole list.
+// recs / unit_base: JsResizeRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown filter / layout / dtype.
+int  js_launch_pack_resize(hipStream_t st, const JsImage* imgs, const uint8_t* dib, const JsResizeRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                           int filter /*JSNOOP_RESIZE_**/, int layout, int dtype, const JsPackArgs& a);

@@ -145,3 +145,9 @@ static inline __host__ __device__ uint32_t js_side_words(uint32_t nmcu, uint32_t
 #define JS_PACK_SEG 512u             /* pixels per unit: two 16-byte loads per lane */
 struct JsPackRec  { uint32_t img, reserved; uint64_t ptr, row_pitch, plane_pitch; };   // destination of image `img`; pitches in bytes, resolved (never 0)
 struct JsPackArgs { int32_t bgr; float scale[3], bias[3]; };
+
+// jsnoop_batch_pack_resized (k_pack_resize, jsnoop_pack_resize.hip): one record per listed destination, resolved like JsPackRec's (pitches never 0, the ROI
+// never empty), and a prefix table in which destination k owns out_h * ceil(out_w / JS_RESIZE_SEG) units -- a unit is one segment of one OUTPUT row.
+#define JS_RESIZE_SEG   256u         /* output pixels per unit: four per lane, the store shapes of the plain pack */
+#define JS_RESIZE_CHUNK 1024u        /* AREA: source pixels of one row a wave stages in LDS at a time (4 KiB per wave) */
+struct JsResizeRec { uint32_t img, out_w, out_h, roi_x, roi_y, roi_w, roi_h, reserved; uint64_t ptr, row_pitch, plane_pitch; };

@@ -229,7 +229,8 @@ class JpegBatch:
         spec = _pack_spec(self._lib, layout, bool(float32), False, None, None)
         return int(self._lib.jsnoop_batch_pack_bytes(self._h, C.byref(spec), i))
 
-    def to_torch(self, images=None, layout="CHW", dtype=None, bgr=False, scale=None, bias=None, stack=False, pad_to=None, out=None):
+    def to_torch(self, images=None, layout="CHW", dtype=None, bgr=False, scale=None, bias=None, stack=False, pad_to=None, out=None,
+                 size=None, filter="bilinear", roi=None):
         """The decoded images as torch tensors on the batch's device: cropped to the SOF dimensions, top-down, three channels (R,G,B, or
         B,G,R with bgr), filled by ONE jsnoop_batch_pack -- no pixel crosses PCIe.
 
@@ -239,6 +240,13 @@ class JpegBatch:
         Default: a list of tensors, one per image, carved out of one allocation.  stack=True: one [N, ...] tensor (ValueError if the dimensions
         differ).  pad_to=(H, W): one zero-filled [N, 3, H, W] / [N, H, W, 3] tensor, every image in its top-left corner.  out=: a tensor
         [N, ...] at least as large as every image, or a list of tensors of the images' exact shapes; inner dimensions contiguous; returned as it is.
+
+        size=(H, W): every image -- or the rectangle roi names in it -- resampled to H x W by ONE jsnoop_batch_pack_resized: the result is one
+        [N, 3, H, W] / [N, H, W, 3] tensor, or out= of exactly that shape (the outer dimension may be strided).  filter: "bilinear" (half-pixel
+        centres, as torch's align_corners=False without antialiasing), "nearest" or "area" (a box filter with fractional coverage, the one for
+        reducing).  roi: None (whole images), one (x, y, w, h) for all, or a list with one per image, in the coordinates of the cropped
+        top-down image.  With H x W equal to the rectangle's size every filter returns its pixels unchanged.  size= excludes stack and pad_to;
+        filter (other than the default) or roi without size= is a ValueError.
 
         Calls sync() first (damaged files arrive repaired), synchronises torch's current stream before the pack unless the batch runs on it, and
         waits for the batch's stream -- sync() again, no other stream of the device is waited for -- before it returns: the tensors are ready."""
@@ -257,10 +265,14 @@ class JpegBatch:
             raise ValueError("to_torch: scale / bias belong to dtype=torch.float32")
         if bool(stack) + (pad_to is not None) + (out is not None) > 1:
             raise ValueError("to_torch: stack, pad_to and out exclude each other")
+        if size is None and (roi is not None or filter != "bilinear"):
+            raise ValueError("to_torch: filter and roi belong to size=(H, W)")
         spec = _pack_spec(self._lib, layout, is_f32, bgr, scale, bias)
         chw = layout == "CHW"
         self.sync()
         dev = torch.device("cuda", self.device())
+        if size is not None:
+            return self._to_torch_resized(torch, idx, spec, chw, dtype, dev, stack, pad_to, out, size, filter, roi)
         dims = []
         for i in idx:
             inf = self.info(i)
@@ -325,6 +337,65 @@ class JpegBatch:
             cur.synchronize()
         ind = (C.c_int * len(idx))(*idx)
         self._chk(self._lib.jsnoop_batch_pack(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack")
+        self.sync()                              # waits for the batch's stream alone
+        return result
+
+    def _to_torch_resized(self, torch, idx, spec, chw, dtype, dev, stack, pad_to, out, size, filter, roi):
+        """to_torch(size=...): one [N, ...] tensor filled by one jsnoop_batch_pack_resized.  The batch has been synchronised."""
+        if stack or pad_to is not None:
+            raise ValueError("to_torch: size= excludes stack and pad_to (the result is one tensor already)")
+        filters = {"nearest": capi.RESIZE_NEAREST, "bilinear": capi.RESIZE_BILINEAR, "area": capi.RESIZE_AREA}
+        if filter not in filters:
+            raise ValueError("to_torch: filter must be \"bilinear\", \"nearest\" or \"area\"")
+        try:
+            H, W = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError("to_torch: size must be (H, W)") from None
+        if not (1 <= H <= 32767 and 1 <= W <= 32767):
+            raise ValueError(f"to_torch: size = ({H}, {W}): each of 1 .. 32767")
+        n = len(idx)
+        if roi is None:
+            rois = [(0, 0, 0, 0)] * n
+        elif len(roi) == 4 and all(np.isscalar(v) for v in roi):
+            rois = [tuple(int(v) for v in roi)] * n
+        else:
+            rois = [tuple(int(v) for v in r) for r in roi]
+            if len(rois) != n or any(len(r) != 4 for r in rois):
+                raise ValueError(f"to_torch: roi must be one (x, y, w, h) or a list of {n} of them")
+        for k, (x, y, w, h) in enumerate(rois):
+            inf = self.info(idx[k])
+            if roi is not None and (min(x, y) < 0 or w < 1 or h < 1 or x + w > inf["dim_x"] or y + h > inf["dim_y"]):
+                raise ValueError(f"to_torch: roi {(x, y, w, h)} leaves image {idx[k]} of {inf['dim_x']} x {inf['dim_y']}")
+        shape = (n, 3, H, W) if chw else (n, H, W, 3)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape:
+                raise ValueError(f"to_torch: with size= out must be one tensor of shape {list(shape)}")
+            if out.device != dev:
+                raise ValueError(f"to_torch: out is on {out.device}, the batch on {dev}")
+            if out.dtype != dtype:
+                raise ValueError(f"to_torch: out is {out.dtype}, asked for {dtype}")
+            result = out
+        else:
+            result = torch.empty(shape, dtype=dtype, device=dev)
+        if not n:
+            return result
+        elem = 4 if dtype == torch.float32 else 1
+        dst = (capi.ResizeDst * n)()
+        for k in range(n):
+            t = result[k]
+            st = t.stride()
+            if st[2] != 1 or (not chw and st[1] != 3) or min(st) < 1:
+                raise ValueError(f"to_torch: destination {k}: the inner dimensions must be contiguous (strides {st})")
+            dst[k].ptr = t.data_ptr()
+            dst[k].row_pitch = (st[1] if chw else st[0]) * elem
+            dst[k].plane_pitch = st[0] * elem if chw else 0
+            dst[k].out_w, dst[k].out_h = W, H
+            dst[k].roi_x, dst[k].roi_y, dst[k].roi_w, dst[k].roi_h = rois[k]
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        ind = (C.c_int * n)(*idx)
+        self._chk(self._lib.jsnoop_batch_pack_resized(self._h, C.byref(spec), filters[filter], ind, n, dst), "batch_pack_resized")
         self.sync()                              # waits for the batch's stream alone
         return result
 
@@ -471,8 +542,8 @@ class JobFileResult:
             self.batch = b
 
     def to_torch(self, **kw):
-        """JpegBatch.to_torch for this file alone: one tensor ([3, dim_y, dim_x] / [dim_y, dim_x, 3]; with stack / pad_to / a tensor out, the
-        [1, ...] tensor).  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        """JpegBatch.to_torch for this file alone: one tensor ([3, dim_y, dim_x] / [dim_y, dim_x, 3]; with stack / pad_to / size / a tensor out,
+        the [1, ...] tensor).  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
         if self.batch is None:
             raise RuntimeError("to_torch: this result holds no resident image (status %s)" % self.status)
         r = self.batch.to_torch(images=[self.image], **kw)
