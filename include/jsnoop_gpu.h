@@ -419,6 +419,59 @@ typedef struct JsnoopResizeDst {
 int          jsnoop_batch_pack_resized(JsnoopBatch*, const JsnoopPackSpec* spec, int filter,
                                        const int* images, int n, const JsnoopResizeDst* dst);
 
+/* ---- coefficient tensors: the DCT blocks of a decoded batch by component, in caller-owned device memory --------------------------------
+ * The third sibling of the two packs, for the decode's other product.  The coefficient arena holds [blocks][64] dequantised int16 in
+ * natural order and DECODE order (MCU after MCU, the components interleaved inside the MCU), with only the DC difference in slot 0.
+ * jsnoop_batch_pack_coefs turns any subset of it into one tensor per destination -- one component of one image -- in ONE kernel launch:
+ * blocks in raster order of that component's own block grid, the true (cumulative) DC in slot 0.
+ *
+ * Block grid.  `comp` counts the scan's components from 0 (0 = Y).  Component c has samp_h[c] x samp_v[c] blocks per MCU; its grid is
+ * bw = mcu_xmax * samp_h[c] by bh = mcu_ymax * samp_v[c] blocks, MCU padding included (jsnoop_batch_coef_grid).  Block (bx, by) is block
+ * (by % samp_v) * samp_h + (bx % samp_h) of that component in MCU (bx / samp_h, by / samp_v).
+ *
+ * What an element is.  Element (bx, by, k) for natural index k != 0 is the arena's value, bit for bit: (int16)(level * dqt[k]) with the
+ * multipliers jsnoop_batch_image_dqt returns.  For natural index 0 it is the block's cumulative DC -- the running sum of the dequantised
+ * differences in wrapping int16 arithmetic, restarted at every restart interval -- never the difference.  Baseline and progressive images
+ * mean the same thing: a progressive file that carries a baseline file's coefficients gives that file's tensors.  An image decoded with
+ * decode_ac = 0 gives what the Full-IDCT kernels leave for it: zeros in slots 1..63, the cumulative DC in slot 0.
+ *
+ * Forms.  JSNOOP_COEF_BLOCKS: [bh][bw][64], element (bx, by, k) at ptr + by * row_pitch + (bx * 64 + k) * elem; plane_pitch is ignored.
+ * JSNOOP_COEF_FREQ: [64][bh][bw], element at ptr + k * plane_pitch + by * row_pitch + bx * elem.  JSNOOP_COEF_I16: elem 2, the arena's
+ * int16 as it is; JSNOOP_COEF_F32: elem 4, (float)value, exact.  JSNOOP_COEF_NATURAL: k = row * 8 + column, the arena's order;
+ * JSNOOP_COEF_ZIGZAG: position z holds natural index zigzag[z] (T.81 Figure A.6).  Dense pitches (what 0 means): BLOCKS row_pitch =
+ * bw * 64 * elem; FREQ row_pitch = bw * elem, plane_pitch = bh * row_pitch.  Only addressed elements are written: pitch gaps and
+ * everything around a destination keep their bytes.
+ *
+ * Ordering: jsnoop_batch_pack's -- enqueued on the batch's stream behind the decode enqueued last (both halves of a two-stream decode
+ * included), not waited for; a call after jsnoop_batch_sync sees the repaired arena, a call before it sees what the parallel path left.
+ * After a DC-only fast-form decode (jsnoop_batch_last_form == 2) the arena does not hold the blocks: the call then does what
+ * jsnoop_batch_read_coefs does, decodes the batch once more through the Full-IDCT kernels and waits for it, and jsnoop_batch_last_form
+ * goes 2 -> 1.  That is the one case in which this call decodes again.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: a NULL batch or one not yet decoded; an image index out of
+ * range; comp at or past the image's component count; a NULL destination; a non-zero `reserved`; a pitch below the dense size; a pointer
+ * or pitch that is not a multiple of elem; an unknown layout, dtype, order or struct_size (read like JsnoopPackSpec's: shorter accepted
+ * with the lacking fields at their defaults, longer refused).  n == 0 is 0; images == NULL means images 0 .. n - 1; an image may be listed
+ * several times (once per component is the normal use).
+ *
+ * jsnoop_batch_image_dqt: the 64 multipliers the decode used for that component, natural order, host arithmetic only.  The library keeps
+ * ONE table per component: for a baseline image the table its component selects when the scan starts, for a progressive image the
+ * definition of the selected destination the file's header walk ended with -- a file that redefines a table between scans is dequantised
+ * with, and reports, that one table.                                                                                                 */
+#define JSNOOP_COEF_BLOCKS  0
+#define JSNOOP_COEF_FREQ    1
+#define JSNOOP_COEF_I16     0
+#define JSNOOP_COEF_F32     1
+#define JSNOOP_COEF_NATURAL 0
+#define JSNOOP_COEF_ZIGZAG  1
+typedef struct JsnoopCoefSpec { uint32_t struct_size; int32_t layout, dtype, order; } JsnoopCoefSpec;
+typedef struct JsnoopCoefDst  { void* ptr; uint64_t row_pitch, plane_pitch; uint32_t comp, reserved; } JsnoopCoefDst;   /* device pointer; pitches in bytes, 0 = dense */
+void         jsnoop_coef_spec_defaults(JsnoopCoefSpec* out);                                   /* BLOCKS, I16, NATURAL; NULL tolerated */
+int          jsnoop_batch_coef_grid(const JsnoopBatch*, int i, int comp, unsigned* bw, unsigned* bh);        /* host arithmetic; 0 / -1 */
+uint64_t     jsnoop_batch_coef_bytes(const JsnoopBatch*, const JsnoopCoefSpec*, int i, int comp);            /* dense size; 0 = bad argument */
+int          jsnoop_batch_pack_coefs(JsnoopBatch*, const JsnoopCoefSpec*, const int* images, int n, const JsnoopCoefDst* dst);
+int          jsnoop_batch_image_dqt(const JsnoopBatch*, int i, int comp, uint16_t* out64);     /* natural order; host only; 0 / -1 */
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

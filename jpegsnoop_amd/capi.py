@@ -70,6 +70,22 @@ class ResizeDst(C.Structure):
                 ("roi_x", C.c_uint32), ("roi_y", C.c_uint32), ("roi_w", C.c_uint32), ("roi_h", C.c_uint32)]
 
 
+COEF_BLOCKS, COEF_FREQ = 0, 1
+COEF_I16, COEF_F32 = 0, 1
+COEF_NATURAL, COEF_ZIGZAG = 0, 1
+COEF_TILE = 64          # JS_COEF_TILE of csrc/jsnoop_types.h: blocks of one block row a wave moves at a time (the frequency-major form's transposition tile)
+
+
+class CoefSpec(C.Structure):
+    """JsnoopCoefSpec of include/jsnoop_gpu.h: what jsnoop_batch_pack_coefs writes (block- or frequency-major, int16 or float32, natural or zig-zag order)."""
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("dtype", C.c_int32), ("order", C.c_int32)]
+
+
+class CoefDst(C.Structure):
+    """JsnoopCoefDst of include/jsnoop_gpu.h: one destination in device memory -- component `comp` of the image listed at the same place; pitches in bytes, 0 = dense."""
+    _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64), ("comp", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -195,6 +211,11 @@ SIGNATURES = {
     "jsnoop_batch_pack": (_i, [_p, C.POINTER(PackSpec), _PI, _i, C.POINTER(PackDst)]),
     "jsnoop_batch_pack_resized": (_i, [_p, C.POINTER(PackSpec), _i, _PI, _i, C.POINTER(ResizeDst)]),
     "jsnoop_batch_device": (_i, [_p]),
+    "jsnoop_coef_spec_defaults": (None, [C.POINTER(CoefSpec)]),
+    "jsnoop_batch_coef_grid": (_i, [_p, _i, _i, _PU, _PU]),
+    "jsnoop_batch_coef_bytes": (C.c_uint64, [_p, C.POINTER(CoefSpec), _i, _i]),
+    "jsnoop_batch_pack_coefs": (_i, [_p, C.POINTER(CoefSpec), _PI, _i, C.POINTER(CoefDst)]),
+    "jsnoop_batch_image_dqt": (_i, [_p, _i, _i, C.POINTER(C.c_uint16)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

@@ -258,6 +258,12 @@ public:
     // (jsnoop_batch_pack_resized: a rectangle of every listed file at its destination's size, filter = JSNOOP_RESIZE_*; same ordering)
     bool     BatchPackResized(const JsnoopPackSpec& spec, int filter, const std::vector<int>& files, const std::vector<JsnoopResizeDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_resized(m_b, &spec, filter, files.data(), (int)files.size(), dst.data()) == 0; }
+    // the DCT coefficients of the listed files, one destination per (file, dst[k].comp): blocks in raster order of the component's block grid, cumulative DC in
+    // natural index 0 (jsnoop_batch_pack_coefs: one launch for the whole list, same ordering; jsnoop_coef_spec_defaults fills a spec)
+    bool     BatchPackCoefs(const JsnoopCoefSpec& spec, const std::vector<int>& files, const std::vector<JsnoopCoefDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack_coefs(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    bool     BatchCoefGrid(int nFileInd, int nComp, unsigned& nBlkW, unsigned& nBlkH) const { return jsnoop_batch_coef_grid(m_b, nFileInd, nComp, &nBlkW, &nBlkH) == 0; }
+    bool     BatchImageDqt(int nFileInd, int nComp, uint16_t* anDqt64) const { return jsnoop_batch_image_dqt(m_b, nFileInd, nComp, anDqt64) == 0; }   // natural order
     bool     BatchGetBitmap(int nFileInd, std::vector<uint8_t>& dib, unsigned& nX, unsigned& nY)
     {
         unsigned info[16]; if (jsnoop_batch_image_info(m_b, nFileInd, info)) return false;

@@ -127,6 +127,7 @@ struct JsnoopBatch {
     uint8_t* h_pack = nullptr; size_t h_pack_cap = 0; uint8_t* d_pack = nullptr; size_t d_pack_cap = 0; hipEvent_t ev_pack = nullptr;
     int  pack(const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);   // jsnoop_pack.cpp
     int  pack_resized(const JsnoopPackSpec* spec, int filter, const int* images, int n, const JsnoopResizeDst* dst);   // jsnoop_pack.cpp; the same block and event
+    int  pack_coefs(const JsnoopCoefSpec* spec, const int* images, int n, const JsnoopCoefDst* dst);   // jsnoop_coef.cpp; the same block and event
     int  pack_block(size_t total);               // h_pack ready to be rewritten and at least `total` bytes large
     int  pack_send(size_t total);                // h_pack -> d_pack on the batch stream, ev_pack behind the copy
     JsDeviceArenas dev; JsArenaCaps cap;
@@ -217,3 +218,4 @@ void js_batch_rewind(JsnoopBatch* b, const JsBatchMark& m);
 uint64_t js_prog_device_bytes(const JsnoopBatch* b);                   // jsnoop_progressive.cpp: the table / interval / work-list buffer
 void js_prog_mark(const JsnoopBatch* b, size_t* m5);
 void js_prog_rewind(JsnoopBatch* b, const size_t* m5);
+int  js_prog_dqt(const JsnoopBatch* b, uint32_t i, uint32_t comp, uint16_t* out64);   // the multipliers k_prog_finalize uses for component comp of image i, natural order

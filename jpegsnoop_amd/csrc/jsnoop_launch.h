@@ -91,3 +91,7 @@ int  js_launch_pack_rgb(hipStream_t st, const JsImage* imgs, const uint8_t* dib,
 // recs / unit_base: JsResizeRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown filter / layout / dtype.
 int  js_launch_pack_resize(hipStream_t st, const JsImage* imgs, const uint8_t* dib, const JsResizeRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                            int filter /*JSNOOP_RESIZE_**/, int layout, int dtype, const JsPackArgs& a);
+// k_pack_coefs (jsnoop_coef.hip): the coefficient arena of a decoded batch -> caller-owned device memory, one tensor per listed component, ONE launch for the whole list.
+// recs / unit_base: JsCoefRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown layout / dtype / order.
+int  js_launch_pack_coefs(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsCoefRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                          int layout /*JSNOOP_COEF_BLOCKS / _FREQ*/, int dtype /*JSNOOP_COEF_I16 / _F32*/, int order /*JSNOOP_COEF_NATURAL / _ZIGZAG*/);

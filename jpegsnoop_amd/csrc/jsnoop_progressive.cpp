@@ -256,6 +256,12 @@ static size_t js_prog_buf_bytes(const JsProgBatch* g)
            up(nimg * 16) + up(nsc * 4) + up((nsc + (size_t)g->nlev) * 4) + up((nimg + 1) * 4);
 }
 uint64_t js_prog_device_bytes(const JsnoopBatch* b) { return js_prog_count(b) ? (uint64_t)js_prog_buf_bytes(b->prog) * 2 : 0; }   // (js_prog_upload allocates twice the layout)
+int js_prog_dqt(const JsnoopBatch* b, uint32_t i, uint32_t comp, uint16_t* out64)
+{
+    if (!b->prog || i >= b->prog->frames.size() || comp >= 3u) { js_set_error("image_dqt: no progressive image %u", i); return -1; }
+    for (int k = 0; k < 64; k++) out64[k] = (uint16_t)b->prog->frames[i].qnat[comp][k];
+    return 0;
+}
 void js_prog_mark(const JsnoopBatch* b, size_t* m)
 {
     const JsProgBatch* g = b->prog;

@@ -151,3 +151,13 @@ struct JsPackArgs { int32_t bgr; float scale[3], bias[3]; };
 #define JS_RESIZE_SEG   256u         /* output pixels per unit: four per lane, the store shapes of the plain pack */
 #define JS_RESIZE_CHUNK 1024u        /* AREA: source pixels of one row a wave stages in LDS at a time (4 KiB per wave) */
 struct JsResizeRec { uint32_t img, out_w, out_h, roi_x, roi_y, roi_w, roi_h, reserved; uint64_t ptr, row_pitch, plane_pitch; };
+
+// jsnoop_batch_pack_coefs (k_pack_coefs, jsnoop_coef.hip): one record per listed destination -- one component of one image, everything the kernel needs of it
+// resolved on the host -- and a prefix table in which destination k owns bh * ceil(bw / JS_COEF_TILE) units: a unit is a run of up to JS_COEF_TILE blocks,
+// consecutive in bx, of one row of the component's block grid -- the work of one wave at a time.  Block (bx, by) of the component is block
+// coef_off + ((by / sv) * mcu_xmax + bx / sh) * bpm + first + (by % sv) * sh + bx % sh of the arena.
+#define JS_COEF_TILE 64u             /* blocks per unit: eight 16-byte loads per lane; one frequency of a full tile is 128 contiguous int16 bytes */
+struct JsCoefRec { uint64_t ptr, row_pitch, plane_pitch, coef_off; uint32_t bw, bh, sh, sv, first, bpm, mcu_xmax, tiles; };   // pitches in bytes, resolved (never 0); tiles = ceil(bw / JS_COEF_TILE)
+// natural index of zig-zag position z (T.81 Figure A.6)
+#define JS_ZIGZAG_NATURAL { 0, 1, 8,16, 9, 2, 3,10, 17,24,32,25,18,11, 4, 5, 12,19,26,33,40,48,41,34, 27,20,13, 6, 7,14,21,28, \
+                           35,42,49,56,57,50,43,36, 29,22,15,23,30,37,44,51, 58,59,52,45,38,31,39,46, 53,60,61,54,47,55,62,63 }

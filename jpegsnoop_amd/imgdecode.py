@@ -418,6 +418,107 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_read_coefs(self._h, i, out.ctypes.data, inf["total_blocks"]), "batch_read_coefs")
         return out
 
+    def coef_grid(self, i, comp):
+        """(bw, bh): the block grid of component comp (0 = Y) of image i, MCU padding included (jsnoop_batch_coef_grid)."""
+        bw, bh = C.c_uint(), C.c_uint()
+        self._chk(self._lib.jsnoop_batch_coef_grid(self._h, int(i), int(comp), C.byref(bw), C.byref(bh)), "batch_coef_grid")
+        return int(bw.value), int(bh.value)
+
+    def dqt(self, i, comp):
+        """The 64 multipliers the decode used for component comp of image i, natural order (jsnoop_batch_image_dqt): every coefficient is
+        int16(level * dqt[k])."""
+        out = np.zeros(64, np.uint16)
+        self._chk(self._lib.jsnoop_batch_image_dqt(self._h, int(i), int(comp), out.ctypes.data_as(C.POINTER(C.c_uint16))), "batch_image_dqt")
+        return out
+
+    def coefs_to_torch(self, images=None, comps=None, layout="blocks", dtype=None, zigzag=False, out=None):
+        """The DCT coefficients of the decoded images as torch tensors on the batch's device, filled by ONE jsnoop_batch_pack_coefs -- no
+        coefficient crosses PCIe.  Returns, per listed image, a list with one tensor per component.
+
+        images: indices into the batch, any order (None = all).  comps: the components wanted of every image, counted from 0 = Y (None = all
+        the image has).  layout "blocks" -> [bh, bw, 64], "freq" -> [64, bh, bw], (bw, bh) = coef_grid(i, comp): blocks in raster order of the
+        component's own grid, MCU padding included.  Natural index 0 holds the cumulative DC, the others the dequantised values
+        int16(level * dqt(i, comp)[k]).  dtype: torch.int16 (default) or torch.float32 (exact).  zigzag: position z holds natural index
+        zigzag[z] instead of k = row * 8 + column.  out=: a list (per image) of lists (per component) of tensors of exactly these shapes, on the
+        batch's device, of the dtype asked for, inner dimensions contiguous (the outer ones may be strided); returned as it is.
+
+        Calls sync() first (damaged files arrive repaired; after a DC-only fast-form decode the call decodes once more, last_form() goes
+        2 -> 1), synchronises torch's current stream before the launch unless the batch runs on it, and waits for the batch's stream before it
+        returns: the tensors are ready."""
+        import torch
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"coefs_to_torch: image index {i} out of range, the batch holds {n_all}")
+        if layout not in ("blocks", "freq"):
+            raise ValueError("coefs_to_torch: layout must be \"blocks\" or \"freq\"")
+        if dtype is None:
+            dtype = torch.int16
+        if dtype not in (torch.int16, torch.float32):
+            raise ValueError("coefs_to_torch: dtype must be torch.int16 or torch.float32")
+        freq, elem = layout == "freq", 4 if dtype == torch.float32 else 2
+        spec = capi.CoefSpec()
+        self._lib.jsnoop_coef_spec_defaults(C.byref(spec))
+        spec.layout = capi.COEF_FREQ if freq else capi.COEF_BLOCKS
+        spec.dtype = capi.COEF_F32 if dtype == torch.float32 else capi.COEF_I16
+        spec.order = capi.COEF_ZIGZAG if zigzag else capi.COEF_NATURAL
+        self.sync()
+        dev = torch.device("cuda", self.device())
+        want, per_image = [], []                     # (image, component, shape) of every destination, in the order of the result; destinations per listed image
+        for i in idx:
+            ncomp = self.info(i)["ncomp"]
+            cs = list(range(ncomp)) if comps is None else [int(c) for c in comps]
+            per_image.append(len(cs))
+            for c in cs:
+                if not 0 <= c < ncomp:
+                    raise IndexError(f"coefs_to_torch: component {c} of image {i}, which has {ncomp}")
+                bw, bh = self.coef_grid(i, c)
+                want.append((i, c, (64, bh, bw) if freq else (bh, bw, 64)))
+        if out is not None:
+            rows = [list(r) for r in out]
+            if len(rows) != len(idx) or [len(r) for r in rows] != per_image:
+                raise ValueError(f"coefs_to_torch: out must hold {len(idx)} lists of {per_image} tensors")
+            views, result = [t for r in rows for t in r], out
+            for k, t in enumerate(views):
+                i, c, shp = want[k]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shp:
+                    raise ValueError(f"coefs_to_torch: out for component {c} of image {i} must be a tensor of shape {list(shp)}")
+                if t.device != dev:
+                    raise ValueError(f"coefs_to_torch: out for component {c} of image {i} is on {t.device}, the batch on {dev}")
+                if t.dtype != dtype:
+                    raise ValueError(f"coefs_to_torch: out for component {c} of image {i} is {t.dtype}, asked for {dtype}")
+        else:
+            sizes = [shp[0] * shp[1] * shp[2] for _, _, shp in want]
+            flat = torch.empty(sum(sizes), dtype=dtype, device=dev)
+            views, off = [], 0
+            for (_, _, shp), sz in zip(want, sizes):
+                views.append(flat[off:off + sz].view(shp))
+                off += sz
+            result, k = [], 0
+            for m in per_image:
+                result.append(views[k:k + m])
+                k += m
+        if not want:
+            return result
+        dst = (capi.CoefDst * len(want))()
+        for k, t in enumerate(views):
+            st, shp = t.stride(), want[k][2]
+            ok = (st[2] == 1 and st[1] >= shp[2] and st[0] >= st[1] * shp[1]) if freq else (st[2] == 1 and st[1] == 64 and st[0] >= 64 * shp[1])
+            if not ok and t.numel():
+                raise ValueError(f"coefs_to_torch: destination {k}: the inner dimensions must be contiguous (strides {st})")
+            dst[k].ptr = t.data_ptr()
+            dst[k].row_pitch = (st[1] if freq else st[0]) * elem
+            dst[k].plane_pitch = st[0] * elem if freq else 0
+            dst[k].comp, dst[k].reserved = want[k][1], 0
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        ind = (C.c_int * len(want))(*[w[0] for w in want])
+        self._chk(self._lib.jsnoop_batch_pack_coefs(self._h, C.byref(spec), ind, len(want), dst), "batch_pack_coefs")
+        self.sync()                              # waits for the batch's stream alone
+        return result
+
     def dib_checksums(self):
         out = np.zeros(len(self), np.uint64)
         self._chk(self._lib.jsnoop_batch_dib_hashes(self._h, out.ctypes.data), "batch_dib_hashes")
@@ -548,6 +649,15 @@ class JobFileResult:
             raise RuntimeError("to_torch: this result holds no resident image (status %s)" % self.status)
         r = self.batch.to_torch(images=[self.image], **kw)
         return r[0] if isinstance(r, list) else r
+
+    def coefs_to_torch(self, **kw):
+        """JpegBatch.coefs_to_torch for this file alone: a list with one tensor per component.  Valid inside the callback, or until
+        JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("coefs_to_torch: this result holds no resident image (status %s)" % self.status)
+        out = kw.pop("out", None)
+        r = self.batch.coefs_to_torch(images=[self.image], out=None if out is None else [out], **kw)
+        return r[0]
 
     def __repr__(self):
         return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
