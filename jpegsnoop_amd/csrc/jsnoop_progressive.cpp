@@ -47,7 +47,8 @@ bool build_table(const RawDht& h, JsProgTable* t)                // T.81 Annex C
 }  // namespace
 
 // One parsed progressive file: frame, every scan with the tables in force at its SOS and its restart intervals, dependency levels.
-struct ProgImage { JsImage im; JsProgFrame fr; std::vector<JsProgScan> scans; std::vector<JsProgTable> tabs; std::vector<JsProgSeg> segs; std::vector<int> level; int nlev = 1; };
+struct ProgImage { JsImage im; JsProgFrame fr; std::vector<JsProgScan> scans; std::vector<JsProgTable> tabs; std::vector<JsProgSeg> segs; std::vector<int> level; int nlev = 1;
+                   bool lacks = false; };                          // lacks: a scan with fewer restart intervals than its units need (part of the picture was never coded)
 
 // Walks the file and fills P.  `d` supplies the preview state and the log sink and receives the geometry (js_geometry), like the
 // decoder object of the baseline path; its table state is reset first.
@@ -129,18 +130,22 @@ static int prog_parse(JsnoopDecoder* d, const uint8_t* f, size_t n, ProgImage* P
             }
             // entropy data: up to the next marker that is neither stuffing nor RSTn; split at the RSTn markers
             sc.seg_first = (uint32_t)segs.size(); sc.rst_interval = rst_interval;
-            size_t q = end, s0 = end;
+            // Fill bytes (B.1.1.2: FF bytes in front of a marker) belong to no interval: a reader that runs past its interval's data must
+            // get zero bits there, not eight ones.  [fill0, fill1) = the run of FF bytes that ends at the FF under q, if any.
+            size_t q = end, s0 = end, fill0 = 0, fill1 = (size_t)-1;
             while (q < n) {
                 q = js_next_ff(f, q, n);                                     // (sixteen bytes per step: every byte of every scan passes here)
                 if (q >= n) break;
                 if (f[q] == 0xFF && q + 1 < n && f[q + 1] != 0x00) {
-                    if (f[q + 1] >= 0xD0 && f[q + 1] <= 0xD7) { segs.push_back({ (uint32_t)s0, (uint32_t)q }); q += 2; s0 = q; continue; }
-                    if (f[q + 1] == 0xFF) { q++; continue; }                 // fill byte
+                    const size_t data_end = fill1 == q ? fill0 : q;
+                    if (f[q + 1] >= 0xD0 && f[q + 1] <= 0xD7) { segs.push_back({ (uint32_t)s0, (uint32_t)data_end }); q += 2; s0 = q; continue; }
+                    if (f[q + 1] == 0xFF) { if (fill1 != q) fill0 = q; fill1 = ++q; continue; }   // fill byte, if a marker follows the run
+                    segs.push_back({ (uint32_t)s0, (uint32_t)data_end }); s0 = (size_t)-1;
                     break;
                 }
                 q++;
             }
-            segs.push_back({ (uint32_t)s0, (uint32_t)q });
+            if (s0 != (size_t)-1) segs.push_back({ (uint32_t)s0, (uint32_t)q });
             sc.nseg = (uint32_t)segs.size() - sc.seg_first;
             scans.push_back(sc);
             pos = q; continue;
@@ -182,6 +187,7 @@ static int prog_parse(JsnoopDecoder* d, const uint8_t* f, size_t n, ProgImage* P
         const uint32_t units = sc.ncomp > 1 ? im.mcu_xmax * im.mcu_ymax : sc.nbx * sc.nby;
         const uint32_t want = sc.rst_interval ? (units + sc.rst_interval - 1) / sc.rst_interval : 1;
         if (sc.nseg > want) sc.nseg = want;                        // surplus RSTn: ignore what follows the last expected interval
+        if (sc.nseg < want) P->lacks = true;                       // missing intervals: their units keep what earlier scans left, the file is flagged
     }
 
     // Scans that touch different coefficients are independent (a DC scan: slot 0 of its components; an AC scan, first or
@@ -224,6 +230,7 @@ struct JsProgBatch {
     std::vector<JsProgFrame> frames; std::vector<JsProgScan> scans; std::vector<JsProgTable> tabs; std::vector<JsProgSeg> segs;
     std::vector<int> level; int nlev = 0;                         // per scan; levels are per image, level L of every image decodes in launch L
     std::vector<uint32_t> first_scan;                              // per image: its first scan (+ end sentinel)
+    std::vector<uint8_t> lacks;                                    // per image: some scan has fewer restart intervals than it needs (host knowledge: no kernel sees it)
     void* d_buf = nullptr; size_t d_cap = 0; bool dirty = true;
     // device views into d_buf (valid after js_prog_upload)
     JsProgFrame* d_frames = nullptr; JsProgScan* d_scans = nullptr; JsProgTable* d_tabs = nullptr; JsProgSeg* d_segs = nullptr;
@@ -233,13 +240,13 @@ struct JsProgBatch {
 };
 size_t js_prog_count(const JsnoopBatch* b) { return b->prog ? b->prog->frames.size() : 0; }
 void js_prog_dirty(JsnoopBatch* b) { if (b->prog) b->prog->dirty = true; }   // a tuning change: the work lists are rebuilt at the next decode
-void js_prog_clear(JsnoopBatch* b) { if (b->prog) { JsProgBatch* g = b->prog; g->frames.clear(); g->scans.clear(); g->tabs.clear(); g->segs.clear(); g->level.clear(); g->first_scan.clear(); g->nlev = 0; g->dirty = true; } }
+void js_prog_clear(JsnoopBatch* b) { if (b->prog) { JsProgBatch* g = b->prog; g->frames.clear(); g->scans.clear(); g->tabs.clear(); g->segs.clear(); g->level.clear(); g->first_scan.clear(); g->lacks.clear(); g->nlev = 0; g->dirty = true; } }
 void js_prog_free(JsnoopBatch* b) { if (b->prog) { if (b->prog->d_buf) hipFree(b->prog->d_buf); delete b->prog; b->prog = nullptr; } }
 // image `src` once more as image `dst` (tile): same scans, tables and intervals (file-relative), its own frame entry
 void js_prog_dup(JsnoopBatch* b, uint32_t src, uint32_t dst)
 {
     JsProgBatch* g = b->prog;
-    g->frames.push_back(g->frames[src]);
+    g->frames.push_back(g->frames[src]); g->lacks.push_back(g->lacks[src]);
     const uint32_t s0 = g->first_scan[src], s1 = g->first_scan[src + 1];
     g->first_scan.back() = (uint32_t)g->scans.size();            // sentinel becomes the first scan of dst
     for (uint32_t q = s0; q < s1; q++) { JsProgScan sc = g->scans[q]; sc.img = dst; g->scans.push_back(sc); g->level.push_back(g->level[q]); }
@@ -272,7 +279,7 @@ void js_prog_rewind(JsnoopBatch* b, const size_t* m)
     JsProgBatch* g = b->prog;
     if (!g || g->frames.size() <= m[0]) return;
     g->frames.resize(m[0]); g->scans.resize(m[1]); g->level.resize(m[1]); g->tabs.resize(m[2]); g->segs.resize(m[3]); g->nlev = (int)m[4];
-    g->first_scan.resize(m[0] ? m[0] + 1 : 0); g->dirty = true;
+    g->first_scan.resize(m[0] ? m[0] + 1 : 0); g->lacks.resize(m[0]); g->dirty = true;
 }
 
 int JsnoopBatch::add_progressive(JsnoopDecoder* d, const uint8_t* f, size_t n)
@@ -286,7 +293,7 @@ int JsnoopBatch::add_progressive(JsnoopDecoder* d, const uint8_t* f, size_t n)
     if (idx < 0) return -1;
     const uint32_t tab0 = (uint32_t)g->tabs.size(), seg0 = (uint32_t)g->segs.size();
     if (g->first_scan.empty()) g->first_scan.push_back(0);
-    g->frames.push_back(P.fr);
+    g->frames.push_back(P.fr); g->lacks.push_back(P.lacks ? 1 : 0);
     g->tabs.insert(g->tabs.end(), P.tabs.begin(), P.tabs.end());
     g->segs.insert(g->segs.end(), P.segs.begin(), P.segs.end());
     for (size_t q = 0; q < P.scans.size(); q++) {
@@ -384,7 +391,7 @@ int JsnoopBatch::sync_progressive()
     std::vector<uint32_t> st((size_t)n * 4, 0);
     if (d2h_staged(st.data(), prog->d_status, st.size() * 4)) return -1;            // (through the page-locked landing buffer; it synchronises the stream)
     host_flags.assign(n, 0); host_path.assign(n, 3u);
-    for (uint32_t i = 0; i < n; i++) host_flags[i] = st[(size_t)i * 4] ? JSNOOP_FLAG_BAD_CODE : 0u;
+    for (uint32_t i = 0; i < n; i++) host_flags[i] = (st[(size_t)i * 4] || prog->lacks[i]) ? JSNOOP_FLAG_BAD_CODE : 0u;
     return 0;
 }
 

@@ -178,7 +178,7 @@ __device__ __forceinline__ uint32_t prog_interval(R& r, const bool writer, const
                 const PGeo& g = ci == 0 ? g0 : ci == 1 ? g1 : g2;                                                  // (selects, no indexed arrays)
                 const JsProgTable& Tdc = s_tab[(dcpack >> (8u * ci)) & 255u];
                 const uint32_t hs = ncomp > 1 ? g.hs : 1u, vs = ncomp > 1 ? g.vs : 1u;
-                for (uint32_t v = 0; v < vs; v++) for (uint32_t h = 0; h < hs; h++) {
+                for (uint32_t v = 0; v < vs && !bad; v++) for (uint32_t h = 0; h < hs && !bad; h++) {     // (a stop ends the MCU at once: the `break` below leaves the h loop only)
                     // interleaved (A.2.2): block (v, h) of the component in MCU u -- the arena's rows ARE in that order; else the component's own grid
                     int16_t* blk = cbase + (ncomp > 1 ? (size_t)u * g.bpm + g.first + v * hs + h : cur.row()) * 64;
                     if (ah == 0) {

@@ -16,8 +16,14 @@ Conventions
   `ac_tab` ((counts[16], symbols) tables handed in instead of the optimal ones, or a function of the scan's symbol
   frequencies that returns one; dc_tab is a list per scan component), `dc_ids`
   / `ac_id` (table destinations 0..3) and `extra_dht` (list of (class, id, table) segments written in front of the scan).
+  Two hooks write IRREGULAR streams token by token (tests/prog_damage_cases.py): `tokens` (a function of the scan's token list
+  that returns the list to code instead; the optimal tables are made from what it returns, so a symbol no encoder would write
+  still gets a code) and `bytes` (a function of the scan's entropy-coded bytes, RSTn markers included, that returns the bytes
+  to write instead).
 * `decode(file)` -> Decoded: frame, coefficient arrays as a conforming decoder holds them at EOI, and one event record per
-  scan (see `decode`).
+  scan (see `decode`).  It asserts on the first irregular symbol: it is the STRICT mode.
+* `decode(file, lenient=True)` -> what a decoder that goes on after damage holds at EOI, by the rules in front of
+  `_decode_scan_lenient` (T.81 Annex G plus the damage contract of DESIGN.md 4.5), with the record of what went wrong where.
 """
 from __future__ import annotations
 
@@ -216,7 +222,7 @@ def _category(a):
     return int(a).bit_length()
 
 
-# tokens of a scan: (0, table slot, symbol) | (1, value, nbits) | (2, restart number, 0)
+# tokens of a scan: (0, table slot, symbol) | (1, value, nbits) | (2, restart number, 0) | (3, bits to drop, 0): see _emit
 def _scan_tokens(frame, coefs, sc, ri, max_corr=937):
     ss, se, ah, al, comps = sc["ss"], sc["se"], sc["ah"], sc["al"], sc["comps"]
     T = []
@@ -331,17 +337,29 @@ def _scan_tokens(frame, coefs, sc, ri, max_corr=937):
 
 
 def _emit(tokens, tables):
-    """tokens -> list of interval byte strings (between them: RSTn)."""
+    """tokens -> list of interval byte strings (between them: RSTn).  Token kind 3 (tests/prog_damage_cases.py) CUTS the interval:
+    (3, n, 0) drops the last n bits written and what is then left of a begun byte (the interval ends on a whole byte, without
+    the padding ones), and every further token of the interval."""
     codes = [_codes(t) if t is not None else None for t in tables]
-    ivs = []; w = _Bits()
+    ivs = []; w = _Bits(); wrote = []; dead = False
     for kind, a, b in tokens:
-        if kind == 0:
-            code, ln = codes[a][b]; w.put(code, ln)
-        elif kind == 1:
-            w.put(a, b)
+        if kind == 2:
+            if not dead:
+                w.flush()
+            ivs.append((bytes(w.out), a)); w = _Bits(); wrote = []; dead = False
+        elif dead:
+            continue
+        elif kind == 3:
+            keep = max(0, sum(n for _v, n in wrote) - a) // 8 * 8
+            w = _Bits(); dead = True
+            for v, n in wrote:
+                n2 = min(n, keep); w.put(v >> (n - n2), n2); keep -= n2
         else:
-            w.flush(); ivs.append((bytes(w.out), a)); w = _Bits()
-    w.flush(); ivs.append((bytes(w.out), None))
+            v, n = codes[a][b] if kind == 0 else (a, b)
+            w.put(v, n); wrote.append((v & ((1 << n) - 1), n))
+    if not dead:
+        w.flush()
+    ivs.append((bytes(w.out), None))
     out = bytearray()
     for data, r in ivs:
         out += data
@@ -367,6 +385,8 @@ def encode_progressive(frame, coefs, script, com_len=None, max_corr=937):
         if want is not None and want != ri:
             ri = int(want); out += _seg(0xDD, ri.to_bytes(2, "big"))
         tokens = _scan_tokens(frame, coefs, sc, ri, max_corr)
+        if sc.get("tokens") is not None:
+            tokens = list(sc["tokens"](tokens))
         ns = len(sc["comps"]); dc = sc["ss"] == 0
         for cls, ident, tab in sc.get("extra_dht", []):
             out += _dht(cls, ident, tab)
@@ -386,7 +406,10 @@ def encode_progressive(frame, coefs, script, com_len=None, max_corr=937):
         for i, c in enumerate(sc["comps"]):
             p += bytes([c + 1, (ids[i] << 4) if dc else ids[i]])
         p += bytes([sc["ss"], sc["se"], sc["ah"] << 4 | sc["al"]])
-        out += _seg(0xDA, p) + _emit(tokens, tables)
+        ecs = _emit(tokens, tables)
+        if sc.get("bytes") is not None:
+            ecs = bytes(sc["bytes"](ecs))
+        out += _seg(0xDA, p) + ecs
     return bytes(out + b"\xFF\xD9")
 
 
@@ -502,14 +525,25 @@ def _split_intervals(f, start):
     return ivs, ff00, q
 
 
-def decode(f):
+def decode(f, lenient=False, variant=None):
     """Decodes a SOF0 / SOF2 Huffman file sequentially.  Returns Decoded with .frame, .coefs and .scans: per scan a dict
     comps ss se ah al dri, start / end (file offsets of the entropy data), intervals [(start, end)], ff00 [file offsets],
     eobruns [(unit the run starts on, length as coded, i.e. including that block)], eob_after_coefs (EOBn symbols read after at
     least one coefficient of the same block), zrl [(unit, position k before the ZRL, position after it)], stretches [(correction bits, kind,
     unit)] with kind 'sym' / 'zrl' (read while a (run, 1) symbol / a ZRL is worked off) or 'tail' (after EOBn / inside a run), max_code
-    (longest Huffman code used), code_lens (histogram 1..16), dc_ids / ac_ids (table destinations), units, overrun."""
+    (longest Huffman code used), code_lens (histogram 1..16), dc_ids / ac_ids (table destinations), units, overrun.
+
+    lenient=True (SOF2 only; the file may end anywhere behind its first SOS): nothing in the entropy-coded data is refused.  Decoded
+    gains .flagged (what JSNOOP_FLAG_BAD_CODE must say) and per scan: units, want (intervals the scan needs), stops [(interval,
+    unit, reason)] with reason 'no_code' / 'dc_category' / 'run_past_se' / 'refine_s', overran [(interval, unit, what was being
+    read when the first bit that was never there was consumed: 'code' / 'value' / 'sign' / 'correction' / 'eob_length' / 'dc_bit')], missing / surplus (interval counts), irregular [(interval, unit, what)] for what is accepted: 'dc_wide'
+    (category 12..15), 'zrl_out' (a ZRL that leaves the band), 'run_out' (a refinement run longer than the zeros left),
+    'bit_set' (a correction bit on a coefficient whose bit Al is set), 'eobrun_cut' (an end-of-band run that outlasts its
+    interval).  `variant` names one deliberately WRONG reading of the contract (tests/test_prog_damage_cases.py shows that the
+    catalogue refuses each): 'stop_scan', 'discard_block', 'refuse_dc12', 'flag_surplus', 'no_flag_missing', 'carry_eobrun'."""
     D = Decoded(); n = len(f); assert f[:2] == b"\xFF\xD8"
+    if lenient:
+        D.flagged = False
     dht = {}; qt = {}; ri = 0; pos = 2; frame = None
     while pos + 4 <= n:
         assert f[pos] == 0xFF, "marker expected at %d" % pos
@@ -548,6 +582,13 @@ def decode(f):
                       ah=seg[3 + 2 * ns] >> 4, al=seg[3 + 2 * ns] & 15, dri=ri,
                       dc_ids=[seg[2 + 2 * i] >> 4 for i in range(ns)], ac_ids=[seg[2 + 2 * i] & 15 for i in range(ns)])
             start = pos + ln
+            if lenient:
+                assert D.sof == 0xC2
+                ivs, end = _split_intervals_lenient(f, start)
+                sc.update(start=start, end=end, intervals=[(a, e) for a, _d, e in ivs])
+                _decode_scan_lenient(D, sc, [d for _a, d, _e in ivs], dht, variant)
+                D.scans.append(sc)
+                pos = end; continue
             ivs, ff00, end = _split_intervals(f, start)
             sc.update(start=start, end=end, ff00=ff00, intervals=[(a, e) for a, _d, e in ivs])
             _decode_scan(D, sc, [d for _a, d, _e in ivs], dht)
@@ -698,6 +739,212 @@ def _decode_scan(D, sc, ivs, dht):
         if r.pos > r.len:
             sc["overrun"] += 1
     sc["max_code"] = max((l for l in range(17) if lens[l]), default=0)
+
+
+# ------------------------------------------------------------------------------------------- the decoder that goes on after damage
+def _split_intervals_lenient(f, start):
+    """Entropy-coded data from `start`, whatever it holds: [(file offset, bytes with the stuffing removed, end offset)] per
+    restart interval and the offset where the scan ends (a marker that is neither RSTn nor stuffing, or the end of the file).
+    FF 00 is the data byte FF (B.1.1.5).  Fill bytes precede MARKERS (B.1.1.2): the FF bytes in front of an RSTn or of the
+    marker that ends the scan belong to neither interval; FF bytes in front of FF 00, or at the very end of a cut file, precede
+    no marker and are data."""
+    ivs = []; cur = bytearray(); s0 = q = start; n = len(f)
+    while q < n:
+        if f[q] != 0xFF:
+            cur.append(f[q]); q += 1; continue
+        e = q
+        while e < n and f[e] == 0xFF:
+            e += 1
+        nx = f[e] if e < n else None
+        if nx is None:
+            cur += b"\xFF" * (e - q); q = e
+        elif nx == 0:
+            cur += b"\xFF" * (e - q); q = e + 1
+        elif 0xD0 <= nx <= 0xD7:
+            ivs.append((s0, bytes(cur), q)); cur = bytearray(); q = e + 1; s0 = q
+        else:
+            ivs.append((s0, bytes(cur), q)); return ivs, e - 1
+    ivs.append((s0, bytes(cur), q))
+    return ivs, q
+
+
+class _Stop(Exception):
+    pass
+
+
+def _book(table):
+    """(code lengths in use, {(length, code): symbol}) (Annex C): a damaged file is small and brings tables of its own, a dictionary
+    costs less to build than the 16-bit look-ahead table of the strict mode."""
+    codes = {(ln, code): sym for sym, (code, ln) in _codes(table).items()}
+    return sorted({ln for ln, _c in codes}), codes
+
+
+def _w16(v):
+    return ((int(v) + 0x8000) & 0xFFFF) - 0x8000
+
+
+def _decode_scan_lenient(D, sc, ivs, dht, variant=None):
+    """One progressive scan of a file that may be damaged.  The rules (T.81 Annex G, and for what G leaves open the contract of
+    DESIGN.md 4.5):
+    * the unit of failure is the (scan, restart interval) pair.  Inside an interval decoding STOPS at a code that matches nothing
+      (16 bits are consumed), a DC category above 15, an AC-first symbol whose run carries k past Se, a refinement symbol with
+      s not in {0, 1}.  What was stored before the stop stays -- in a refinement block the corrections of the earlier symbols of
+      that block too --, the units behind it keep what earlier scans left, the other intervals and scans go on;
+    * past the end of an interval's bytes the reader delivers zero bits and decoding goes on; the interval OVERRAN when it
+      consumed one of them.  An end-of-band run that outlasts its interval is dropped;
+    * accepted: DC categories 12..15; a ZRL that leaves the band (the block ends); a refinement (run, 1) that finds fewer than
+      run + 1 zero-history positions (its correction bits are spent, the new value is dropped);
+    * every store wraps to int16: pred * (1 << Al), extend(bits(s), s) * (1 << Al); a correction bit leaves a coefficient alone
+      when its bit Al is already set;
+    * fewer intervals than the scan needs: the missing units are untouched, the file is flagged; surplus intervals are ignored
+      and not flagged.
+    The file is flagged when an interval stopped or overran or a scan lacks intervals."""
+    frame, coefs = D.frame, D.coefs
+    ss, se, ah, al, comps = sc["ss"], sc["se"], sc["ah"], sc["al"], sc["comps"]
+    inter = len(comps) > 1
+    if inter:
+        units = frame.mcu_x * frame.mcu_y
+    else:
+        nby, nbx = frame.coded(comps[0]); units = nby * nbx
+    ri = sc["dri"] or units
+    want = _cdiv(units, ri)
+    sc.update(units=units, want=want, stops=[], overran=[], irregular=[], missing=max(0, want - len(ivs)), surplus=max(0, len(ivs) - want))
+    if sc["missing"] and variant != "no_flag_missing":
+        D.flagged = True
+    if sc["surplus"] and variant == "flag_surplus":
+        D.flagged = True
+    dc_lut = [_book(dht[(0, i)]) if (ss == 0 and ah == 0) else None for i in sc["dc_ids"]]
+    ac_lut = _book(dht[(1, sc["ac_ids"][0])]) if se > 0 else None
+    p1, m1 = 1 << al, -(1 << al)
+    dc_max = 11 if variant == "refuse_dc12" else 15
+
+    at = [0, 0]                                                        # interval and unit being decoded
+
+    def over(r, what):
+        if r.pos > r.len and not (sc["overran"] and sc["overran"][-1][0] == at[0]):
+            sc["overran"].append((at[0], at[1], what)); D.flagged = True
+
+    def huff(r, book):
+        p = r.peek16()
+        for ln in book[0]:
+            sym = book[1].get((ln, p >> (16 - ln)))
+            if sym is not None:
+                r.pos += ln; over(r, "code")
+                return sym
+        r.pos += 16; over(r, "code")
+        raise _Stop("no_code")
+
+    def take(r, n, what):
+        v = r.bits(n); over(r, what)
+        return v
+
+    def unit_blocks(u):
+        if inter:
+            my, mx = divmod(u, frame.mcu_x)
+            for slot, c in enumerate(comps):
+                h, v = frame.hv[c]
+                for y in range(v):
+                    for x in range(h):
+                        yield slot, coefs[c][my * v + y, mx * h + x]
+        else:
+            yield 0, coefs[comps[0]][u // nbx, u % nbx]
+
+    def correct(r, blk, k, iv, u):
+        v = int(blk[k])
+        if take(r, 1, "correction"):
+            if v & p1:
+                sc["irregular"].append((iv, u, "bit_set"))
+            else:
+                blk[k] = _w16(v + (p1 if v >= 0 else m1))
+
+    eobrun = 0
+    for iv in range(min(want, len(ivs))):
+        data = ivs[iv]
+        r = _Reader(data) if len(data) < 512 else _Chunked(data)
+        u0, u1 = iv * ri, min(units, iv * ri + ri)
+        pred = [0] * len(comps)
+        if variant != "carry_eobrun":
+            eobrun = 0
+        u = u0; entry = None
+        try:
+            while u < u1:
+                at[0], at[1] = iv, u
+                if ss > 0 and eobrun and ah == 0:                      # AC first: the blocks of an end-of-band run are not coded
+                    hop = min(eobrun, u1 - u); eobrun -= hop; u += hop
+                    continue
+                for slot, blk in unit_blocks(u):
+                    entry = (blk, blk.copy())
+                    if ss == 0 and ah == 0:                            # DC first (G.1.2.1)
+                        s = huff(r, dc_lut[slot])
+                        if s > dc_max:
+                            raise _Stop("dc_category")
+                        if s > 11:
+                            sc["irregular"].append((iv, u, "dc_wide"))
+                        pred[slot] += _extend(take(r, s, "value"), s) if s else 0
+                        blk[0] = _w16(pred[slot] * (1 << al))
+                    elif ss == 0:                                      # DC refinement
+                        if take(r, 1, "dc_bit"):
+                            blk[0] = _w16(int(blk[0]) | p1)
+                    elif ah == 0:                                      # AC first (G.1.2.2)
+                        k = ss
+                        while k <= se:
+                            rs = huff(r, ac_lut); rr, s = rs >> 4, rs & 15
+                            if s:
+                                k += rr
+                                if k > se:
+                                    raise _Stop("run_past_se")
+                                blk[k] = _w16(_extend(take(r, s, "value"), s) * (1 << al)); k += 1
+                            elif rr == 15:
+                                if k + 16 > se + 1:
+                                    sc["irregular"].append((iv, u, "zrl_out"))
+                                k += 16
+                            else:
+                                eobrun = (1 << rr) + take(r, rr, "eob_length") - 1
+                                break
+                    else:                                              # AC refinement (G.1.2.3)
+                        k = ss
+                        if eobrun and not blk[ss:se + 1].any():        # inside a run, nothing to correct
+                            eobrun -= 1
+                            continue
+                        if not eobrun:
+                            while k <= se:
+                                rs = huff(r, ac_lut); rr, s = rs >> 4, rs & 15
+                                newv = 0
+                                if s:
+                                    if s != 1:
+                                        raise _Stop("refine_s")
+                                    newv = p1 if take(r, 1, "sign") else m1
+                                elif rr != 15:
+                                    eobrun = (1 << rr) + take(r, rr, "eob_length")
+                                    break
+                                while k <= se:                         # pass rr zero-history positions, correct the others on the way
+                                    if blk[k]:
+                                        correct(r, blk, k, iv, u)
+                                    else:
+                                        rr -= 1
+                                        if rr < 0:
+                                            break
+                                    k += 1
+                                if k > se:
+                                    sc["irregular"].append((iv, u, "run_out" if s else "zrl_out"))
+                                elif newv:
+                                    blk[k] = newv
+                                k += 1
+                        if eobrun:
+                            while k <= se:
+                                if blk[k]:
+                                    correct(r, blk, k, iv, u)
+                                k += 1
+                            eobrun -= 1
+                u += 1
+            if eobrun:
+                sc["irregular"].append((iv, u1 - 1, "eobrun_cut"))
+        except _Stop as e:
+            sc["stops"].append((iv, u, e.args[0])); D.flagged = True
+            if variant == "discard_block":
+                entry[0][...] = entry[1]
+            if variant == "stop_scan":
+                break
 
 
 # ------------------------------------------------------------------------------------------- what the decoder leaves behind

@@ -7,6 +7,11 @@ The codec is held from four sides before anything on the GPU trusts it:
 * its baseline writer, decoded by the project's own oracle, gives the dequantised truth;
 * the repository's C generator (oracle/jpeg_synth.c) agrees with its decoder, progressive against baseline form;
 * libjpeg (through Pillow, where present) reads every catalogue file to the pixels of the baseline form of its truth.
+
+The LENIENT mode of the decoder (decode(file, lenient=True): the truth for damaged files, tests/prog_damage_cases.py) is held from two:
+* on every well-formed file it is the strict mode, with nothing on its record;
+* where libjpeg tolerates the damage the way the contract does, libjpeg reads the damaged file to the pixels of the baseline form of
+  the lenient truth.
 """
 import io
 import json
@@ -121,3 +126,63 @@ def test_libjpeg_reads_random_scripts():
         a, b = [np.asarray(Image.open(io.BytesIO(d))) for d in (c.file, c.base)]
         assert np.array_equal(a, b), c.name
         assert same_on_coded_blocks(c.frame, c.truth, c.coefs) is None, c.name
+
+
+# ------------------------------------------------------------------------------------------------------------ the lenient mode
+def _lenient_is_strict(c):
+    L = P.decode(c.file, lenient=True)
+    assert len(L.scans) == len(c.dec.scans) and not L.flagged, c.name
+    assert all(np.array_equal(a, b) for a, b in zip(L.coefs, c.truth)), c.name
+    for s in L.scans:
+        assert not (s["stops"] or s["overran"] or s["irregular"] or s["missing"] or s["surplus"]), (c.name, s)
+
+
+@pytest.mark.parametrize("name", PC.NAMES)
+def test_lenient_mode_is_the_strict_mode_on_the_catalogue(name):
+    _lenient_is_strict(PC.built(name))
+
+
+def test_lenient_mode_is_the_strict_mode_on_random_scripts():
+    for c in PC.build_random(32):
+        _lenient_is_strict(c)
+
+
+# Damaged catalogue cases that libjpeg decodes the way the contract says: data that ends early reads as zero bits, an interval that is
+# not there leaves its blocks alone, fill bytes and a surplus RSTn at the end are passed over, a ZRL may leave the band, a correction
+# bit leaves a coefficient whose bit is set alone.
+# DROPPED, because libjpeg recovers differently: every case whose damage is in front of an RSTn of a scan that goes on
+# (runout_interval_emptied_ac_first, runout_cut_inside_value_bits, runout_cut_inside_an_eobn_length_field, runout_file_cut_inside_scan_1,
+# runout_last_rstn_deleted, runout_last_rstn_deleted_dc, accepted_eobrun_32767_in_an_interval_of_3: libjpeg resynchronises on the
+# marker numbers and carries or discards state differently), the two runs longer than the zeros left (libjpeg stores the new value one
+# position PAST the band, the contract drops it), the two DC scans with irregular component lists (libjpeg refuses the scan), the
+# stop cases (libjpeg goes on behind a bad code with a zero), the wide-DC cases (no baseline form) and runout_file_ends_in_an_ff_that_is_data
+# (libjpeg waits for the byte behind an FF and, at the end of the file, takes neither).
+LIBJPEG_AGREES = [
+    "runout_file_cut_inside_the_last_scan", "runout_file_cut_inside_the_last_scan_no_restarts", "runout_file_cut_exactly_at_an_rstn",
+    "runout_interval_emptied_dc", "runout_interval_emptied_refinement", "runout_cut_inside_a_code", "runout_cut_inside_a_correction_stretch",
+    "runout_surplus_rstn_in_the_middle", "runout_surplus_rstn_at_the_end", "runout_fill_bytes_before_an_rstn",
+    "runout_fill_bytes_behind_a_cut_interval", "runout_stuffed_ff_is_the_last_byte_of_a_cut_interval",
+    "accepted_zrl_out_of_the_band_ac_first", "accepted_zrl_out_of_the_band_refinement", "accepted_zrl_out_of_the_band_refinement_over_history",
+    "accepted_correction_bit_on_a_set_bit",
+]
+
+
+@pytest.mark.parametrize("name", LIBJPEG_AGREES)
+def test_libjpeg_reads_damaged_files_to_the_lenient_truth(name):
+    pytest.importorskip("PIL")
+    from PIL import Image, ImageFile
+    import prog_damage_cases as DC
+    c = DC.built(name)
+    assert c.base is not None
+    old = ImageFile.LOAD_TRUNCATED_IMAGES
+    ImageFile.LOAD_TRUNCATED_IMAGES = True
+    try:
+        out = []
+        for data in (c.file, c.base):
+            im = Image.open(io.BytesIO(data)); im.load()
+            out.append(np.asarray(im))
+    finally:
+        ImageFile.LOAD_TRUNCATED_IMAGES = old
+    assert out[0].shape == out[1].shape and np.array_equal(out[0], out[1])
+    if not c.same_as_clean and c.file != c.clean_file:                 # (and the damage shows: these are not the pixels of the whole file)
+        assert not np.array_equal(out[0], np.asarray(Image.open(io.BytesIO(c.clean_file))))
