@@ -472,6 +472,38 @@ uint64_t     jsnoop_batch_coef_bytes(const JsnoopBatch*, const JsnoopCoefSpec*, 
 int          jsnoop_batch_pack_coefs(JsnoopBatch*, const JsnoopCoefSpec*, const int* images, int n, const JsnoopCoefDst* dst);
 int          jsnoop_batch_image_dqt(const JsnoopBatch*, int i, int comp, uint16_t* out64);     /* natural order; host only; 0 / -1 */
 
+/* ---- colour statistics of a whole batch: one row of JSNOOP_STATS_WORDS words per listed image, on the device ---------------------------
+ * The fourth sibling: jsnoop_batch_color_stats(b, i, ...) costs a fill, a launch, a copy and a wait per image (and a second round for
+ * an image with more than 10 range events).  jsnoop_batch_pack_stats computes the rows of any subset of a decoded batch in TWO kernel
+ * launches, from the retained int16 planes (the batch needs want_planes), into caller-owned device memory.
+ *
+ * What a row is.  Row k holds exactly the words jsnoop_batch_color_stats(b, images[k], histo_en, out) writes: the layout above
+ * (JSNOOP_STATS_WORDS), records seeded with 0, sums modulo 2^32, over the MCU-padded picture img_x x img_y; a fresh budget of 10 YCC
+ * range events per image, counted in the reference's visiting order -- raster order, within a pixel Y over, Y under, Cb over, Cb under,
+ * Cr over, Cr under; histo_en == 0 leaves only the clip counters (words 37..48).  Baseline and progressive images, images decoded by the
+ * Full-IDCT kernels and by the DC-only fast form are treated alike: the call reads the planes and never decodes again
+ * (jsnoop_batch_last_form is unchanged).  The preview shift of an image descriptor is part of the shared per-pixel arithmetic and is
+ * carried along, but no public call sets it on a user batch: through this door it is always the default (no shift) and untested.
+ *
+ * dst: device memory, a multiple of 4; row k starts at word k * row_pitch_words (0 = dense, else at least JSNOOP_STATS_WORDS).  All
+ * JSNOOP_STATS_WORDS words of every listed row are defined by the call (rows are zeroed on the stream first: a second call into the same
+ * memory gives the same rows); words between JSNOOP_STATS_WORDS and the pitch keep their content.  totals: NULL, or device memory
+ * [n][6]: how many range events of each kind image k has IN ALL, indexed like words 37..42 (Y<0, Y>255, Cb<0, Cb>255, Cr<0, Cr>255) --
+ * the row's counters stop at 10 together, these do not.  images: n indices into the batch, any order, any subset, repeats allowed (NULL =
+ * images 0..n-1).
+ *
+ * Ordering: jsnoop_batch_pack's -- enqueued on the batch's stream behind the decode enqueued last (both halves of a two-stream decode
+ * included), not waited for; a call after jsnoop_batch_sync sees the repaired planes, a call before it what the parallel path left.
+ * Scratch (a few words per listed image and per picture row) is batch-owned, grown on demand and not part of jsnoop_batch_device_bytes.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: a NULL batch or one not yet decoded; an image index out of
+ * range; a batch without planes; a NULL destination or one that is not a multiple of 4 (totals likewise); a row_pitch_words below
+ * JSNOOP_STATS_WORDS.  n == 0 is 0.
+ *
+ * jsnoop_batch_read_stats: the same rows, dense, into HOST memory through batch-owned device scratch: one D2H copy, one wait.          */
+int          jsnoop_batch_pack_stats(JsnoopBatch*, int histo_en, const int* images, int n, void* dst, uint64_t row_pitch_words, uint32_t* totals);
+int          jsnoop_batch_read_stats(JsnoopBatch*, int histo_en, const int* images, int n, uint32_t* host_dst);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

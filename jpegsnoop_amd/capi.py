@@ -73,6 +73,8 @@ class ResizeDst(C.Structure):
 COEF_BLOCKS, COEF_FREQ = 0, 1
 COEF_I16, COEF_F32 = 0, 1
 COEF_NATURAL, COEF_ZIGZAG = 0, 1
+STATS_WORDS = 2482      # JSNOOP_STATS_WORDS of include/jsnoop_gpu.h: words of one row of colour statistics
+STATS_UNIT = 512        # JS_STATS_UNIT of csrc/jsnoop_types.h: pixels of one picture row a wave takes at a time (k_stats_batch)
 COEF_TILE = 64          # JS_COEF_TILE of csrc/jsnoop_types.h: blocks of one block row a wave moves at a time (the frequency-major form's transposition tile)
 
 
@@ -216,6 +218,8 @@ SIGNATURES = {
     "jsnoop_batch_coef_bytes": (C.c_uint64, [_p, C.POINTER(CoefSpec), _i, _i]),
     "jsnoop_batch_pack_coefs": (_i, [_p, C.POINTER(CoefSpec), _PI, _i, C.POINTER(CoefDst)]),
     "jsnoop_batch_image_dqt": (_i, [_p, _i, _i, C.POINTER(C.c_uint16)]),
+    "jsnoop_batch_pack_stats": (_i, [_p, _i, _PI, _i, _p, C.c_uint64, _p]),
+    "jsnoop_batch_read_stats": (_i, [_p, _i, _PI, _i, _p]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

@@ -262,6 +262,10 @@ public:
     // natural index 0 (jsnoop_batch_pack_coefs: one launch for the whole list, same ordering; jsnoop_coef_spec_defaults fills a spec)
     bool     BatchPackCoefs(const JsnoopCoefSpec& spec, const std::vector<int>& files, const std::vector<JsnoopCoefDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_coefs(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    // the bHistoEn (bHistoEn = false: only bStatClipEn) statistics of the listed files, one row of JSNOOP_STATS_WORDS words each at pDst + k * nRowPitchWords (0 = dense)
+    // in the caller's device memory, from the retained planes (jsnoop_batch_pack_stats: two launches for the whole list, same ordering; pTotals: NULL or [n][6])
+    bool     BatchPackStats(bool bHistoEn, const std::vector<int>& files, void* pDst, uint64_t nRowPitchWords = 0, uint32_t* pTotals = nullptr)
+    { return jsnoop_batch_pack_stats(m_b, bHistoEn ? 1 : 0, files.data(), (int)files.size(), pDst, nRowPitchWords, pTotals) == 0; }
     bool     BatchCoefGrid(int nFileInd, int nComp, unsigned& nBlkW, unsigned& nBlkH) const { return jsnoop_batch_coef_grid(m_b, nFileInd, nComp, &nBlkW, &nBlkH) == 0; }
     bool     BatchImageDqt(int nFileInd, int nComp, uint16_t* anDqt64) const { return jsnoop_batch_image_dqt(m_b, nFileInd, nComp, anDqt64) == 0; }   // natural order
     bool     BatchGetBitmap(int nFileInd, std::vector<uint8_t>& dib, unsigned& nX, unsigned& nY)

@@ -302,6 +302,8 @@ JsnoopBatch::~JsnoopBatch()
     if (ev_up) hipEventDestroy(ev_up);
     if (h_pack) hipHostFree(h_pack);
     if (d_pack) hipFree(d_pack);
+    if (d_stats) hipFree(d_stats);
+    if (d_stats_rows) hipFree(d_stats_rows);
     if (ev_pack) hipEventDestroy(ev_pack);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     for (auto& e : ev2) if (e) hipEventDestroy(e);

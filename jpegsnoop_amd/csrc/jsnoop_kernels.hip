@@ -18,6 +18,7 @@
 #include <atomic>
 #include "jsnoop_types.h"
 #include "jsnoop_launch.h"
+#include "jsnoop_stat_pixel.h"
 
 #define WAVE 64
 // wave vote on a bool: the HIP wrapper __ballot(int) makes the compiler materialise the predicate as 0 / 1 and compare it again (two
@@ -1284,29 +1285,14 @@ __global__ void __launch_bounds__(256) k_dib_checksum(const JsImage* __restrict_
 //  Cr<0, Cr>255): the reference only counts those while fewer than 10 warnings were issued (:4372-4378), which
 //  the host resolves from these totals -- or, when the budget is exceeded, with k_clip_order below.
 // =====================================================================================
-struct StatPix { int pre[3]; int clipv[3]; int fin[3]; int lim[3]; int rgb[3]; };
+// (StatPix and the value part, stat_values, are in jsnoop_stat_pixel.h: jsnoop_stats.hip computes a batch's rows with the same arithmetic)
 __device__ __forceinline__ void stat_pixel(const JsImage& im, const int16_t* __restrict__ pl, uint32_t p, uint32_t shift_ind, StatPix& o)
 {
     const uint32_t W = im.img_x, pw = im.blk_xmax * 8, py = p / W, px = p - py * W;
     const size_t pi = (size_t)py * pw + px, psz = (size_t)pw * im.blk_ymax * 8;
     o.pre[0] = pl[pi]; o.pre[1] = im.ncomp == 3 ? pl[psz + pi] : 0; o.pre[2] = im.ncomp == 3 ? pl[2 * psz + pi] : 0;   // :4683-4693
     const uint32_t mi = (py / im.mcu_h) * (W / im.mcu_w) + px / im.mcu_w;
-    if (mi >= shift_ind) { o.pre[0] += im.shift_y; o.pre[1] += im.shift_cb; o.pre[2] += im.shift_cr; }                   // :4735-4739
-    #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        o.clipv[c] = (o.pre[c] + 1024) / 8;                      // C division, truncates toward zero (:4265-4267)
-        o.fin[c] = min(max(o.clipv[c], 0), 255);                 // CapYccRange
-    }
-    const float kr = 0.299f, kg = 0.587f, kb = 0.114f;
-    const float cr_mul = 2 - 2 * kr, cb_mul = 2 - 2 * kb;
-    const float fy = (float)(o.fin[0] - 128);
-    float r = __fadd_rn(__fmul_rn((float)(o.fin[2] - 128), cr_mul), fy);
-    float b = __fadd_rn(__fmul_rn((float)(o.fin[1] - 128), cb_mul), fy);
-    float g = __fdiv_rn(__fsub_rn(__fsub_rn(fy, __fmul_rn(kb, b)), __fmul_rn(kr, r)), kg);
-    r = __fadd_rn(r, 128.0f); b = __fadd_rn(b, 128.0f); g = __fadd_rn(g, 128.0f);
-    o.lim[0] = (int)r; o.lim[1] = (int)g; o.lim[2] = (int)b;      // CapRgbRange truncates first, then range-checks the ints
-    #pragma unroll
-    for (int c = 0; c < 3; c++) o.rgb[c] = min(max(o.lim[c], 0), 255);
+    stat_values(o, mi >= shift_ind, im);
 }
 
 #define ST_THREADS 256

@@ -95,3 +95,8 @@ int  js_launch_pack_resize(hipStream_t st, const JsImage* imgs, const uint8_t* d
 // recs / unit_base: JsCoefRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown layout / dtype / order.
 int  js_launch_pack_coefs(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsCoefRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                           int layout /*JSNOOP_COEF_BLOCKS / _FREQ*/, int dtype /*JSNOOP_COEF_I16 / _F32*/, int order /*JSNOOP_COEF_NATURAL / _ZIGZAG*/);
+// k_stats_batch / k_stats_order (jsnoop_stats.hip): the colour statistics of every listed row from the retained planes, TWO launches for the whole list.
+// recs / unit_base: JsStatRec and its 64-bit prefix table (jsnoop_types.h), both in device memory; tot (JS_STATS_TOT_WORDS words per row) and rowcnt (one word
+// per picture row of every listed row) are scratch the caller zeroed on `st`, as it zeroed the rows; totals_out: null, or [nrec][6].  0, -1 on a launch error.
+int  js_launch_stats_batch(hipStream_t st, const int16_t* planes, const JsStatRec* recs, const uint64_t* unit_base, uint32_t nrec, uint64_t total_units, int hist_en,
+                           uint32_t* tot, uint32_t* rowcnt, uint32_t* totals_out);

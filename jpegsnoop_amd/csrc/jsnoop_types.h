@@ -158,6 +158,13 @@ struct JsResizeRec { uint32_t img, out_w, out_h, roi_x, roi_y, roi_w, roi_h, res
 // coef_off + ((by / sv) * mcu_xmax + bx / sh) * bpm + first + (by % sv) * sh + bx % sh of the arena.
 #define JS_COEF_TILE 64u             /* blocks per unit: eight 16-byte loads per lane; one frequency of a full tile is 128 contiguous int16 bytes */
 struct JsCoefRec { uint64_t ptr, row_pitch, plane_pitch, coef_off; uint32_t bw, bh, sh, sv, first, bpm, mcu_xmax, tiles; };   // pitches in bytes, resolved (never 0); tiles = ceil(bw / JS_COEF_TILE)
+// jsnoop_batch_pack_stats (k_stats_batch / k_stats_order, jsnoop_stats.hip): one record per listed row -- one image, everything the kernels need of it resolved
+// on the host -- and a 64-bit prefix table in which row k owns img_y * ceil(img_x / JS_STATS_UNIT) units: a unit is a run of up to JS_STATS_UNIT pixels of one
+// row of the MCU-padded picture, the work of one wave at a time (a lane owns eight consecutive samples).  row_base: the row's first word in the per-call
+// arena of range-event counts per picture row.
+#define JS_STATS_UNIT 512u           /* pixels per unit: one 16-byte load per lane and plane */
+#define JS_STATS_TOT_WORDS 8u        /* per listed row in scratch: the six range-event totals, padded */
+struct JsStatRec { uint64_t dst, plane_off, psz, row_base; uint32_t img_x, img_y, pw, ncomp, mcu_w, mcu_h, across, shift_ind; int32_t shift_y, shift_cb, shift_cr; uint32_t tiles; };
 // natural index of zig-zag position z (T.81 Figure A.6)
 #define JS_ZIGZAG_NATURAL { 0, 1, 8,16, 9, 2, 3,10, 17,24,32,25,18,11, 4, 5, 12,19,26,33,40,48,41,34, 27,20,13, 6, 7,14,21,28, \
                            35,42,49,56,57,50,43,36, 29,22,15,23,30,37,44,51, 58,59,52,45,38,31,39,46, 53,60,61,54,47,55,62,63 }

@@ -519,6 +519,62 @@ class JpegBatch:
         self.sync()                              # waits for the batch's stream alone
         return result
 
+    def stats_to_torch(self, images=None, histo_en=True, out=None, totals=False):
+        """The bHistoEn (histo_en=False: only bStatClipEn) colour statistics of the decoded images as ONE int32 [n, 2482] tensor on the batch's
+        device: row k is what color_stats(images[k], histo_en) returns (view it with stats_fields), computed from the retained planes by one
+        jsnoop_batch_pack_stats -- two launches for the whole list, no word crosses PCIe.  The batch needs want_planes.
+
+        images: indices into the batch, any order, repeats allowed (None = all).  out=: an int32 tensor [n, >= 2482] on the batch's device whose
+        rows are contiguous (the outer dimension may be strided; columns from 2482 on keep their content); returned as it is.  totals=True:
+        returns (rows, totals), totals an int32 [n, 6] tensor: how many YCC range events of each kind the image has in all, indexed like words
+        37..42 (the row's counters stop at 10 together).
+
+        Calls sync() first (damaged files arrive repaired; never decodes again, last_form() is unchanged), synchronises torch's current stream
+        before the launches unless the batch runs on it, and waits for the batch's stream before it returns: the tensors are ready."""
+        import torch
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"stats_to_torch: image index {i} out of range, the batch holds {n_all}")
+        n = len(idx)
+        self.sync()
+        dev = torch.device("cuda", self.device())
+        if out is None:
+            rows = torch.empty((n, capi.STATS_WORDS), dtype=torch.int32, device=dev)
+        else:
+            rows = out
+            if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < capi.STATS_WORDS:
+                raise ValueError(f"stats_to_torch: out must be a tensor of shape [{n}, >= {capi.STATS_WORDS}]")
+            if rows.device != dev or rows.dtype != torch.int32:
+                raise ValueError(f"stats_to_torch: out is {rows.dtype} on {rows.device}, wanted torch.int32 on {dev}")
+            if n and (rows.stride(1) != 1 or (n > 1 and rows.stride(0) < capi.STATS_WORDS)):
+                raise ValueError(f"stats_to_torch: the rows of out must be contiguous and not overlap (strides {rows.stride()})")
+        tot = torch.empty((n, 6), dtype=torch.int32, device=dev) if totals else None
+        if n:
+            cur = torch.cuda.current_stream(dev)
+            if self._stream != cur.cuda_stream:
+                cur.synchronize()
+            ind = (C.c_int * n)(*idx)
+            pitch = rows.stride(0) if n > 1 else 0
+            self._chk(self._lib.jsnoop_batch_pack_stats(self._h, int(bool(histo_en)), ind, n, rows.data_ptr(), pitch, tot.data_ptr() if totals else None), "batch_pack_stats")
+            self.sync()                          # waits for the batch's stream alone
+        return (rows, tot) if totals else rows
+
+    def stats_all(self, images=None, histo_en=True):
+        """The same rows as a numpy uint32 [n, 2482] array in host memory (jsnoop_batch_read_stats: one D2H copy, one wait)."""
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"stats_all: image index {i} out of range, the batch holds {n_all}")
+        out = np.zeros((len(idx), capi.STATS_WORDS), np.uint32)
+        if idx:
+            self.sync()
+            ind = (C.c_int * len(idx))(*idx)
+            self._chk(self._lib.jsnoop_batch_read_stats(self._h, int(bool(histo_en)), ind, len(idx), out.ctypes.data), "batch_read_stats")
+        return out
+
     def dib_checksums(self):
         out = np.zeros(len(self), np.uint64)
         self._chk(self._lib.jsnoop_batch_dib_hashes(self._h, out.ctypes.data), "batch_dib_hashes")
@@ -622,6 +678,15 @@ def _pack_spec(lib, layout, is_f32, bgr, scale, bias) -> "capi.PackSpec":
 _INFO_KEYS = "dim_x dim_y img_x img_y mcu_w mcu_h mcu_xmax mcu_ymax blk_xmax blk_ymax scan_bytes flags path ncomp file_len total_blocks".split()
 
 
+def stats_fields(row):
+    """Named views of one JSNOOP_STATS_WORDS row (numpy array or torch tensor, any integer dtype): "records" [12, 3] = (min, max, sum) of
+    PreclipY/Cb/Cr, ClipY/Cb/Cr, ClipR/G/B, PreclipR/G/B (signed: view an unsigned row as int32 first), "count", "clip" [13] (Y<0, Y>255,
+    Cb<0, Cb>255, Cr<0, Cr>255, R<0, R>255, G<0, G>255, B<0, B>255, White), "r" / "g" / "b" [128] and "y" [2048]."""
+    if row.shape[-1] != capi.STATS_WORDS or len(row.shape) != 1:
+        raise ValueError("stats_fields: a row of %d words" % capi.STATS_WORDS)
+    return {"records": row[0:36].reshape(12, 3), "count": row[36], "clip": row[37:50], "r": row[50:178], "g": row[178:306], "b": row[306:434], "y": row[434:2482]}
+
+
 class JobFileResult:
     """One file of a JpegJob: status ("ok" / "refused" / "unreadable" / "pending"), kind ("baseline" / "progressive" / None), where it was
     decoded, info (as JpegBatch.info), dib_hash, message.  `batch` / `image` address the file in a borrowed JpegBatch: inside the callback,
@@ -658,6 +723,13 @@ class JobFileResult:
         out = kw.pop("out", None)
         r = self.batch.coefs_to_torch(images=[self.image], out=None if out is None else [out], **kw)
         return r[0]
+
+    def stats_to_torch(self, **kw):
+        """JpegBatch.stats_to_torch for this file alone: the [1, 2482] tensor (with totals=True also the [1, 6] one).  The job needs want_planes.
+        Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("stats_to_torch: this result holds no resident image (status %s)" % self.status)
+        return self.batch.stats_to_torch(images=[self.image], **kw)
 
     def __repr__(self):
         return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
