@@ -504,6 +504,45 @@ int          jsnoop_batch_image_dqt(const JsnoopBatch*, int i, int comp, uint16_
 int          jsnoop_batch_pack_stats(JsnoopBatch*, int histo_en, const int* images, int n, void* dst, uint64_t row_pitch_words, uint32_t* totals);
 int          jsnoop_batch_read_stats(JsnoopBatch*, int histo_en, const int* images, int n, uint32_t* host_dst);
 
+/* ---- coefficient histograms: one row of counts per (image, component), by DCT frequency, on the device ---------------------------------
+ * The fifth sibling, the reduction of the coefficient side: the histogram of every DCT frequency of one component of one image -- what
+ * double-compression detection, quantiser estimation and first-digit statistics start from -- without the tensors ever being written.
+ * jsnoop_batch_pack_coef_hist turns any list of (image, component) pairs of a decoded batch into one row per pair in caller-owned
+ * device memory, in ONE kernel launch behind a small one that initialises the rows.
+ *
+ * What a row is.  Let T be the tensor jsnoop_batch_pack_coefs gives for (image, comp) in BLOCKS / I16 / NATURAL: [bh][bw][64], MCU padding
+ * included, the cumulative DC in natural index 0 (baseline and progressive files mean the same thing; an image decoded with decode_ac = 0
+ * has zeros in 1..63), and q[k] what jsnoop_batch_image_dqt returns.  For an element v at natural index k, x = v when quantised == 0 and
+ * x = v / max(q[k], 1) otherwise: C integer division, truncating toward zero, of the int16 as it stands in the arena -- exact levels
+ * whenever |level * q| <= 32767; where the product wrapped int16 the quotient is what it is.  Position p = 0..63 is natural index p
+ * (JSNOOP_COEF_NATURAL) or natural index zigzag[p] (JSNOOP_COEF_ZIGZAG).  With range R (1..127) and NB = 2 R + 1 a row is 64 * NB + 128
+ * words (jsnoop_coef_hist_words): hist[p][b], uint32 at word p * NB + b, the number of blocks whose x at position p has
+ * clamp(x, -R, R) + R == b -- both end bins saturate; min[p], int32 at word 64 * NB + p, and max[p], int32 at word 64 * NB + 64 + p, the
+ * smallest and largest UNCLAMPED x at that position (every grid has a block: no seed is ever visible).
+ *
+ * dst: device memory, a multiple of 4; row k belongs to (images[k], comps[k]) and starts at word k * row_pitch_words (0 = dense, else at
+ * least the row length).  Any order, any subset, repeats allowed; each row stands alone.  All words of every listed row are defined by the
+ * call (rows are initialised on the stream first: a second call into the same memory gives the same rows); words between the row length
+ * and the pitch keep their bytes.
+ *
+ * Ordering: jsnoop_batch_pack_coefs', word for word -- enqueued on the batch's stream behind the decode enqueued last (both halves of a
+ * two-stream decode included), not waited for; a call after jsnoop_batch_sync sees the repaired arena, a call before it sees what the
+ * parallel path left.  After a DC-only fast-form decode (jsnoop_batch_last_form == 2) the call does what jsnoop_batch_read_coefs does,
+ * decodes the batch once more through the Full-IDCT kernels and waits for it, and jsnoop_batch_last_form goes 2 -> 1.  That is the one
+ * case in which this call decodes again.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: a NULL batch or one not yet decoded; NULL images, comps or
+ * dst; an image index out of range; a comp at or past the image's component count; a dst that is not a multiple of 4; a pitch that is
+ * non-zero and below the row length; a range outside 1..127; an unknown order or struct_size (read like JsnoopCoefSpec's: shorter
+ * accepted with the lacking fields at their defaults, longer refused).  n == 0 is 0.
+ *
+ * jsnoop_batch_read_coef_hist: the same rows, dense, into HOST memory through batch-owned device scratch: one D2H copy, one wait.      */
+typedef struct JsnoopCoefHistSpec { uint32_t struct_size; int32_t order, quantised; uint32_t range; } JsnoopCoefHistSpec;
+void         jsnoop_coef_hist_spec_defaults(JsnoopCoefHistSpec* out);                          /* NATURAL, quantised 1, range 127; NULL tolerated */
+uint32_t     jsnoop_coef_hist_words(const JsnoopCoefHistSpec*);                                /* row length in words; 0 = bad spec */
+int          jsnoop_batch_pack_coef_hist(JsnoopBatch*, const JsnoopCoefHistSpec*, const int* images, const int* comps, int n, void* dst, uint64_t row_pitch_words);
+int          jsnoop_batch_read_coef_hist(JsnoopBatch*, const JsnoopCoefHistSpec*, const int* images, const int* comps, int n, uint32_t* host_dst);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

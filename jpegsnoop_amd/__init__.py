@@ -6,5 +6,5 @@ reference's decoder object, `JpegBatch` is the batched submit, `JpegJob` decodes
 file list over all devices.
 """
 from .capi import load, last_error, LIB_PATH  # noqa: F401
-from .imgdecode import CimgDecode, JpegBatch, JpegJob, JobFileResult, JpegPipeline, dib_checksum_numpy, stats_fields  # noqa: F401
+from .imgdecode import CimgDecode, JpegBatch, JpegJob, JobFileResult, JpegPipeline, dib_checksum_numpy, stats_fields, coef_hist_fields  # noqa: F401
 from .shard import partition_lpt, partition_contiguous, reduce_job_stats  # noqa: F401

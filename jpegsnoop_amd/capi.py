@@ -78,6 +78,29 @@ STATS_UNIT = 512        # JS_STATS_UNIT of csrc/jsnoop_types.h: pixels of one pi
 COEF_TILE = 64          # JS_COEF_TILE of csrc/jsnoop_types.h: blocks of one block row a wave moves at a time (the frequency-major form's transposition tile)
 
 
+COEF_HIST_UNIT = 64     # JS_COEF_HIST_UNIT of csrc/jsnoop_types.h: blocks of one component, in arena order, a wave takes at a time (k_coef_hist)
+COEF_HIST_WAVES = 8     # JS_COEF_HIST_WAVES: waves of a workgroup, which deal the units of one destination inside the workgroup's share among themselves
+COEF_HIST_WG_PER_CU = 2 # JS_COEF_HIST_WG_PER_CU: workgroups per compute unit (fewer if 160 KiB of LDS held fewer histograms of 64 * (2 R + 1) words)
+COEF_HIST_RANGE_MAX = 127
+
+
+def coef_hist_words(range_):
+    """Words of one row of jsnoop_batch_pack_coef_hist: 64 histograms of 2 R + 1 bins, 64 minima, 64 maxima."""
+    return 64 * (2 * range_ + 1) + 128
+
+
+def coef_hist_share(total_units, cus, range_):
+    """Units of one workgroup's contiguous share, as js_launch_coef_hist sizes it for a device of `cus` compute units."""
+    want = min(cus * min(COEF_HIST_WG_PER_CU, 163840 // (256 * (2 * range_ + 1))), -(-total_units // COEF_HIST_WAVES))
+    return -(-total_units // want)
+
+
+class CoefHistSpec(C.Structure):
+    """JsnoopCoefHistSpec of include/jsnoop_gpu.h: what a row of jsnoop_batch_pack_coef_hist counts (natural or zig-zag positions, quantised levels or the arena's
+    values, bins -range .. range)."""
+    _fields_ = [("struct_size", C.c_uint32), ("order", C.c_int32), ("quantised", C.c_int32), ("range", C.c_uint32)]
+
+
 class CoefSpec(C.Structure):
     """JsnoopCoefSpec of include/jsnoop_gpu.h: what jsnoop_batch_pack_coefs writes (block- or frequency-major, int16 or float32, natural or zig-zag order)."""
     _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("dtype", C.c_int32), ("order", C.c_int32)]
@@ -220,6 +243,10 @@ SIGNATURES = {
     "jsnoop_batch_image_dqt": (_i, [_p, _i, _i, C.POINTER(C.c_uint16)]),
     "jsnoop_batch_pack_stats": (_i, [_p, _i, _PI, _i, _p, C.c_uint64, _p]),
     "jsnoop_batch_read_stats": (_i, [_p, _i, _PI, _i, _p]),
+    "jsnoop_coef_hist_spec_defaults": (None, [C.POINTER(CoefHistSpec)]),
+    "jsnoop_coef_hist_words": (C.c_uint32, [C.POINTER(CoefHistSpec)]),
+    "jsnoop_batch_pack_coef_hist": (_i, [_p, C.POINTER(CoefHistSpec), _PI, _PI, _i, _p, C.c_uint64]),
+    "jsnoop_batch_read_coef_hist": (_i, [_p, C.POINTER(CoefHistSpec), _PI, _PI, _i, _p]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

@@ -266,6 +266,10 @@ public:
     // in the caller's device memory, from the retained planes (jsnoop_batch_pack_stats: two launches for the whole list, same ordering; pTotals: NULL or [n][6])
     bool     BatchPackStats(bool bHistoEn, const std::vector<int>& files, void* pDst, uint64_t nRowPitchWords = 0, uint32_t* pTotals = nullptr)
     { return jsnoop_batch_pack_stats(m_b, bHistoEn ? 1 : 0, files.data(), (int)files.size(), pDst, nRowPitchWords, pTotals) == 0; }
+    // the histogram of every DCT frequency of component comps[k] of file files[k], one row of jsnoop_coef_hist_words(&spec) words each at pDst + k * nRowPitchWords
+    // (0 = dense) in the caller's device memory (jsnoop_batch_pack_coef_hist: one launch for the whole list, same ordering; jsnoop_coef_hist_spec_defaults fills a spec)
+    bool     BatchPackCoefHist(const JsnoopCoefHistSpec& spec, const std::vector<int>& files, const std::vector<int>& comps, void* pDst, uint64_t nRowPitchWords = 0)
+    { return files.size() == comps.size() && jsnoop_batch_pack_coef_hist(m_b, &spec, files.data(), comps.data(), (int)files.size(), pDst, nRowPitchWords) == 0; }
     bool     BatchCoefGrid(int nFileInd, int nComp, unsigned& nBlkW, unsigned& nBlkH) const { return jsnoop_batch_coef_grid(m_b, nFileInd, nComp, &nBlkW, &nBlkH) == 0; }
     bool     BatchImageDqt(int nFileInd, int nComp, uint16_t* anDqt64) const { return jsnoop_batch_image_dqt(m_b, nFileInd, nComp, anDqt64) == 0; }   // natural order
     bool     BatchGetBitmap(int nFileInd, std::vector<uint8_t>& dib, unsigned& nX, unsigned& nY)

@@ -304,6 +304,7 @@ JsnoopBatch::~JsnoopBatch()
     if (d_pack) hipFree(d_pack);
     if (d_stats) hipFree(d_stats);
     if (d_stats_rows) hipFree(d_stats_rows);
+    if (d_chist_rows) hipFree(d_chist_rows);
     if (ev_pack) hipEventDestroy(ev_pack);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     for (auto& e : ev2) if (e) hipEventDestroy(e);

@@ -100,3 +100,8 @@ int  js_launch_pack_coefs(hipStream_t st, const int16_t* coef, const int16_t* dc
 // per picture row of every listed row) are scratch the caller zeroed on `st`, as it zeroed the rows; totals_out: null, or [nrec][6].  0, -1 on a launch error.
 int  js_launch_stats_batch(hipStream_t st, const int16_t* planes, const JsStatRec* recs, const uint64_t* unit_base, uint32_t nrec, uint64_t total_units, int hist_en,
                            uint32_t* tot, uint32_t* rowcnt, uint32_t* totals_out);
+// k_coef_hist_init / k_coef_hist (jsnoop_coef_hist.hip): the rows of jsnoop_batch_pack_coef_hist initialised, then filled in ONE launch for the whole list.
+// recs / unit_base: JsCoefHistRec and its 64-bit prefix table (jsnoop_types.h), both in device memory; row k at dst + k * pitch_words words.
+// 0, -1 on a launch error or an unknown order / range.
+int  js_launch_coef_hist(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsCoefHistRec* recs, const uint64_t* unit_base, uint32_t nrec, uint64_t total_units,
+                         int order /*JSNOOP_COEF_NATURAL / _ZIGZAG*/, uint32_t range /*1 .. 127*/, void* dst, uint64_t pitch_words);

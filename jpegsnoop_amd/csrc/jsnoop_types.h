@@ -165,6 +165,18 @@ struct JsCoefRec { uint64_t ptr, row_pitch, plane_pitch, coef_off; uint32_t bw, 
 #define JS_STATS_UNIT 512u           /* pixels per unit: one 16-byte load per lane and plane */
 #define JS_STATS_TOT_WORDS 8u        /* per listed row in scratch: the six range-event totals, padded */
 struct JsStatRec { uint64_t dst, plane_off, psz, row_base; uint32_t img_x, img_y, pw, ncomp, mcu_w, mcu_h, across, shift_ind; int32_t shift_y, shift_cb, shift_cr; uint32_t tiles; };
+// jsnoop_batch_pack_coef_hist (k_coef_hist, jsnoop_coef_hist.hip): one record per listed row -- one component of one image, everything the kernel needs of it
+// resolved on the host -- and a 64-bit prefix table in which row k owns ceil(nblk / JS_COEF_HIST_UNIT) units: a unit is a run of up to JS_COEF_HIST_UNIT of
+// the component's blocks in ARENA order (a histogram does not care about raster order), the work of one wave at a time.  Block n of the component is block
+// coef_off + (n / hv) * bpm + first + n % hv of the arena; hv_magic = 65536 / hv + 1 divides the small sums the kernel meets (below 96) by hv exactly.
+// recip[k]: the reciprocal (js_chist_recip, jsnoop_coef_bin.h) of the divisor of natural index k -- the DQT entry, or 1 where the row holds dequantised values.
+#define JS_COEF_HIST_UNIT 64u        /* blocks per unit: eight 16-byte loads per lane */
+#define JS_COEF_HIST_WAVES 8u        /* waves of a workgroup: they share one histogram in LDS and deal the units of a share among themselves */
+#define JS_COEF_HIST_WG_PER_CU 2u    /* workgroups per compute unit: sixteen waves, four a SIMD at 128 VGPRs; two histograms of up to 65 280 bytes fit the 160 KiB of LDS */
+struct JsCoefHistRec { uint64_t dst, coef_off; uint32_t nblk, hv, first, bpm, hv_magic, pad0, pad1, pad2; uint32_t recip[64]; };
+// zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
+#define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
+                            10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }
 // natural index of zig-zag position z (T.81 Figure A.6)
 #define JS_ZIGZAG_NATURAL { 0, 1, 8,16, 9, 2, 3,10, 17,24,32,25,18,11, 4, 5, 12,19,26,33,40,48,41,34, 27,20,13, 6, 7,14,21,28, \
                            35,42,49,56,57,50,43,36, 29,22,15,23,30,37,44,51, 58,59,52,45,38,31,39,46, 53,60,61,54,47,55,62,63 }

@@ -8,6 +8,7 @@ binding layer here: decode happens in libjsnoop_gpu.so on the GPU.
 """
 from __future__ import annotations
 
+import builtins
 import ctypes as C
 
 import numpy as np
@@ -575,6 +576,92 @@ class JpegBatch:
             self._chk(self._lib.jsnoop_batch_read_stats(self._h, int(bool(histo_en)), ind, len(idx), out.ctypes.data), "batch_read_stats")
         return out
 
+    def _coef_hist_pairs(self, images, comps, what):
+        """The (image, component) pairs of one coefficient-histogram call, checked: images and comps both given -> the pairs (images[k], comps[k]);
+        comps None -> every component of every listed image (images None = all); images None -> the listed components of every image."""
+        n_all = len(self)
+        if images is not None and comps is not None:
+            im, cs = [int(i) for i in images], [int(c) for c in comps]
+            if len(im) != len(cs):
+                raise ValueError(f"{what}: images and comps name pairs and must be equally long ({len(im)} and {len(cs)})")
+            pairs = list(zip(im, cs))
+        else:
+            idx = list(builtins.range(n_all)) if images is None else [int(i) for i in images]
+            for i in idx:
+                if not 0 <= i < n_all:
+                    raise IndexError(f"{what}: image index {i} out of range, the batch holds {n_all}")
+            pairs = [(i, c) for i in idx for c in (builtins.range(self.info(i)["ncomp"]) if comps is None else [int(c) for c in comps])]
+        for i, c in pairs:
+            if not 0 <= i < n_all:
+                raise IndexError(f"{what}: image index {i} out of range, the batch holds {n_all}")
+            if not 0 <= c < self.info(i)["ncomp"]:
+                raise IndexError(f"{what}: component {c} of image {i}, which has {self.info(i)['ncomp']}")
+        return pairs
+
+    def _coef_hist_spec(self, range, quantised, zigzag, what):
+        if not 1 <= int(range) <= capi.COEF_HIST_RANGE_MAX:
+            raise ValueError(f"{what}: range must be 1 .. {capi.COEF_HIST_RANGE_MAX}")
+        spec = capi.CoefHistSpec()
+        self._lib.jsnoop_coef_hist_spec_defaults(C.byref(spec))
+        spec.order = capi.COEF_ZIGZAG if zigzag else capi.COEF_NATURAL
+        spec.quantised, spec.range = int(bool(quantised)), int(range)
+        return spec
+
+    def coef_hist_to_torch(self, images=None, comps=None, range=127, quantised=True, zigzag=False, out=None):
+        """The histogram of every DCT frequency of the listed (image, component) pairs as ONE int32 [n, 64 * (2 * range + 1) + 128] tensor on the
+        batch's device, filled by one jsnoop_batch_pack_coef_hist -- no coefficient tensor is written, no word crosses PCIe.  Returns
+        (pairs, rows): row k belongs to pairs[k] = (image, component); view it with coef_hist_fields(row, range).
+
+        images / comps: both given -> the pairs (images[k], comps[k]), any order, repeats allowed; comps None -> every component of every listed
+        image (images None = all images); images None -> the listed components of every image.  A row counts, per position 0..63 (natural index, or
+        zig-zag position with zigzag=True), the blocks of the component's grid (MCU padding included) by clamp(x, -range, range) + range, x the
+        quantised level (the arena's int16 divided by dqt(i, comp)[k], truncating toward zero; natural index 0 is the cumulative DC) or with
+        quantised=False the dequantised value itself; behind the histograms the smallest and the largest unclamped x of every position.
+        out=: an int32 tensor [n, >= row length] on the batch's device whose rows are contiguous (the outer dimension may be strided; columns
+        behind the row keep their content); returned as it is.
+
+        Calls sync() first (damaged files arrive repaired; after a DC-only fast-form decode the call decodes once more, last_form() goes
+        2 -> 1), synchronises torch's current stream before the launch unless the batch runs on it, and waits for the batch's stream before it
+        returns: the tensor is ready."""
+        import torch
+        spec = self._coef_hist_spec(range, quantised, zigzag, "coef_hist_to_torch")
+        pairs = self._coef_hist_pairs(images, comps, "coef_hist_to_torch")
+        n, words = len(pairs), capi.coef_hist_words(int(range))
+        self.sync()
+        dev = torch.device("cuda", self.device())
+        if out is None:
+            rows = torch.empty((n, words), dtype=torch.int32, device=dev)
+        else:
+            rows = out
+            if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < words:
+                raise ValueError(f"coef_hist_to_torch: out must be a tensor of shape [{n}, >= {words}]")
+            if rows.device != dev or rows.dtype != torch.int32:
+                raise ValueError(f"coef_hist_to_torch: out is {rows.dtype} on {rows.device}, wanted torch.int32 on {dev}")
+            if n and (rows.stride(1) != 1 or (n > 1 and rows.stride(0) < words)):
+                raise ValueError(f"coef_hist_to_torch: the rows of out must be contiguous and not overlap (strides {rows.stride()})")
+        if n:
+            cur = torch.cuda.current_stream(dev)
+            if self._stream != cur.cuda_stream:
+                cur.synchronize()
+            ind, cmp_ = (C.c_int * n)(*[i for i, _ in pairs]), (C.c_int * n)(*[c for _, c in pairs])
+            pitch = rows.stride(0) if n > 1 else 0
+            self._chk(self._lib.jsnoop_batch_pack_coef_hist(self._h, C.byref(spec), ind, cmp_, n, rows.data_ptr(), pitch), "batch_pack_coef_hist")
+            self.sync()                          # waits for the batch's stream alone
+        return pairs, rows
+
+    def coef_hist_all(self, images=None, comps=None, range=127, quantised=True, zigzag=False):
+        """(pairs, rows): the same rows as a numpy uint32 [n, row length] array in host memory (jsnoop_batch_read_coef_hist: one D2H copy, one wait);
+        minima and maxima are signed: view them as int32 (coef_hist_fields does)."""
+        spec = self._coef_hist_spec(range, quantised, zigzag, "coef_hist_all")
+        pairs = self._coef_hist_pairs(images, comps, "coef_hist_all")
+        out = np.zeros((len(pairs), capi.coef_hist_words(int(range))), np.uint32)
+        if pairs:
+            self.sync()
+            n = len(pairs)
+            ind, cmp_ = (C.c_int * n)(*[i for i, _ in pairs]), (C.c_int * n)(*[c for _, c in pairs])
+            self._chk(self._lib.jsnoop_batch_read_coef_hist(self._h, C.byref(spec), ind, cmp_, n, out.ctypes.data), "batch_read_coef_hist")
+        return pairs, out
+
     def dib_checksums(self):
         out = np.zeros(len(self), np.uint64)
         self._chk(self._lib.jsnoop_batch_dib_hashes(self._h, out.ctypes.data), "batch_dib_hashes")
@@ -687,6 +774,18 @@ def stats_fields(row):
     return {"records": row[0:36].reshape(12, 3), "count": row[36], "clip": row[37:50], "r": row[50:178], "g": row[178:306], "b": row[306:434], "y": row[434:2482]}
 
 
+def coef_hist_fields(row, range):
+    """Views (not copies) of one row of coef_hist_to_torch / coef_hist_all (numpy array or torch tensor): (hist [64, 2 * range + 1], min [64], max [64]).
+    A numpy row of an unsigned dtype gives its minima and maxima viewed as int32."""
+    nb = 2 * int(range) + 1
+    if len(row.shape) != 1 or row.shape[0] != 64 * nb + 128:
+        raise ValueError("coef_hist_fields: a row of %d words for range %d" % (64 * nb + 128, int(range)))
+    mn, mx = row[64 * nb:64 * nb + 64], row[64 * nb + 64:]
+    if isinstance(row, np.ndarray) and row.dtype == np.uint32:
+        mn, mx = mn.view(np.int32), mx.view(np.int32)
+    return row[:64 * nb].reshape(64, nb), mn, mx
+
+
 class JobFileResult:
     """One file of a JpegJob: status ("ok" / "refused" / "unreadable" / "pending"), kind ("baseline" / "progressive" / None), where it was
     decoded, info (as JpegBatch.info), dib_hash, message.  `batch` / `image` address the file in a borrowed JpegBatch: inside the callback,
@@ -730,6 +829,17 @@ class JobFileResult:
         if self.batch is None:
             raise RuntimeError("stats_to_torch: this result holds no resident image (status %s)" % self.status)
         return self.batch.stats_to_torch(images=[self.image], **kw)
+
+    def coef_hist_to_torch(self, **kw):
+        """JpegBatch.coef_hist_to_torch for this file alone: (pairs, rows), one row per component (comps= picks some).  Valid inside the callback, or
+        until JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("coef_hist_to_torch: this result holds no resident image (status %s)" % self.status)
+        comps = kw.pop("comps", None)
+        if comps is not None:
+            comps = [int(c) for c in comps]
+            return self.batch.coef_hist_to_torch(images=[self.image] * len(comps), comps=comps, **kw)
+        return self.batch.coef_hist_to_torch(images=[self.image], **kw)
 
     def __repr__(self):
         return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
