@@ -543,6 +543,52 @@ uint32_t     jsnoop_coef_hist_words(const JsnoopCoefHistSpec*);                 
 int          jsnoop_batch_pack_coef_hist(JsnoopBatch*, const JsnoopCoefHistSpec*, const int* images, const int* comps, int n, void* dst, uint64_t row_pitch_words);
 int          jsnoop_batch_read_coef_hist(JsnoopBatch*, const JsnoopCoefHistSpec*, const int* images, const int* comps, int n, uint32_t* host_dst);
 
+/* ---- plane tensors: the Y, Cb, Cr samples of a decoded batch by component, in caller-owned device memory --------------------------------
+ * The sixth sibling, for the decode's third product.  A batch that keeps its planes (want_planes) holds, per image, the reference's
+ * m_pPixValY / Cb / Cr: int16 samples before CapYccRange, three fractional bits, chroma replicated to the luma grid.  The DIB cannot give
+ * them back (the clamp, the float colour lines and the replication are lossy) and jsnoop_batch_read_planes crosses PCIe.
+ * jsnoop_batch_pack_planes turns any subset into one two-dimensional tensor per destination -- one component of one image -- in ONE kernel
+ * launch.  Pure data movement: no sample is recomputed.
+ *
+ * What an element is.  `comp` counts the scan's components from 0 (0 = Y; a one-component image has component 0 only).  P_c is what
+ * jsnoop_batch_read_planes gives for component c of image i: top-down, blk_xmax * 8 samples wide, MCU padding included.  eh = expand_h[c]
+ * and ev = expand_v[c] are the replication factors the decode used: hmax / samp_h[c] and vmax / samp_v[c], integer division, hmax and vmax
+ * the largest sampling factors of the scan (1 for a one-component scan).
+ *   JSNOOP_PLANE_FULL  : dim_x x dim_y (the SOF dimensions); element (x, y) is P_c[y][x].
+ *   JSNOOP_PLANE_NATIVE: ceil(dim_x / eh) x ceil(dim_y / ev); element (x, y) is P_c[y * ev][x * eh].  A decimation of the retained plane,
+ *                        defined for every layout; where the plane is a pure replication it is the component's own sample grid.  For a
+ *                        component with eh = ev = 1 (luma, normally) it equals FULL.
+ *   JSNOOP_PLANE_I16   : elem 2, the plane's int16 as it is.
+ *   JSNOOP_PLANE_U8    : elem 1, min(max((v + 1024) / 8, 0), 255) with C division, truncating toward zero: CapYccRange's value, the 8-bit
+ *                        sample the colour conversion starts from.  After the clamp it equals clamp_s8(v >> 3) + 128 with an arithmetic
+ *                        shift, the form the DIB path uses (a negative numerator differs between the two only below the clamp).
+ *   JSNOOP_PLANE_F32   : elem 4, (float)v * scale[comp] + bias[comp]: one rounded fp32 multiply, then one rounded fp32 add (no FMA).
+ * Element (x, y) lies at ptr + y * row_pitch + x * elem; row_pitch is in bytes, 0 = dense (w * elem).  Only addressed elements are
+ * written: pitch gaps and everything around a destination keep their bytes.  U8 destinations may start at any byte, I16 at any even one.
+ * The preview shift of an image descriptor is not part of the planes (they hold the un-shifted samples) and is not applied.
+ *
+ * Ordering: jsnoop_batch_pack_stats', word for word -- enqueued on the batch's stream behind the decode enqueued last (both halves of a
+ * two-stream decode included), not waited for; a call after jsnoop_batch_sync sees the repaired planes, a call before it what the parallel
+ * path left.  The call reads the planes and never decodes again: jsnoop_batch_last_form is unchanged, also after a DC-only fast-form
+ * decode, whose kernels write the planes too.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: a NULL batch or one not yet decoded; a batch without planes
+ * (want_planes); an image index out of range; comp at or past the image's component count, or above 2; a NULL destination; a non-zero
+ * `reserved`; a row_pitch that is non-zero and below the dense row; a pointer or pitch that is not a multiple of elem; an unknown res,
+ * dtype or struct_size (read like JsnoopPackSpec's: shorter accepted with the lacking fields at their defaults, longer refused).  n == 0
+ * is 0; images == NULL means images 0 .. n - 1; an image may be listed several times (once per component is the normal use).           */
+#define JSNOOP_PLANE_FULL   0
+#define JSNOOP_PLANE_NATIVE 1
+#define JSNOOP_PLANE_I16    0
+#define JSNOOP_PLANE_U8     1
+#define JSNOOP_PLANE_F32    2
+typedef struct JsnoopPlaneSpec { uint32_t struct_size; int32_t res, dtype; float scale[3], bias[3]; } JsnoopPlaneSpec;   /* scale, bias: JSNOOP_PLANE_F32 only, by component */
+typedef struct JsnoopPlaneDst  { void* ptr; uint64_t row_pitch; uint32_t comp, reserved; } JsnoopPlaneDst;               /* device pointer; pitch in bytes, 0 = dense */
+void         jsnoop_plane_spec_defaults(JsnoopPlaneSpec* out);                                 /* FULL, I16, scale 1, bias 0; NULL tolerated */
+int          jsnoop_batch_plane_size(const JsnoopBatch*, const JsnoopPlaneSpec*, int i, int comp, unsigned* w, unsigned* h);   /* host arithmetic; 0 / -1 */
+uint64_t     jsnoop_batch_plane_bytes(const JsnoopBatch*, const JsnoopPlaneSpec*, int i, int comp);                           /* dense size; 0 = bad argument */
+int          jsnoop_batch_pack_planes(JsnoopBatch*, const JsnoopPlaneSpec*, const int* images, int n, const JsnoopPlaneDst* dst);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

@@ -111,6 +111,22 @@ class CoefDst(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64), ("comp", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PLANE_FULL, PLANE_NATIVE = 0, 1
+PLANE_I16, PLANE_U8, PLANE_F32 = 0, 1, 2
+PLANE_SEG = 512         # JS_PLANE_SEG of csrc/jsnoop_types.h: elements of one output row a wave moves at a time (k_pack_planes)
+
+
+class PlaneSpec(C.Structure):
+    """JsnoopPlaneSpec of include/jsnoop_gpu.h: what jsnoop_batch_pack_planes writes (cropped planes or the component's own grid; int16, uint8 or float32 with
+    scale and bias by component)."""
+    _fields_ = [("struct_size", C.c_uint32), ("res", C.c_int32), ("dtype", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class PlaneDst(C.Structure):
+    """JsnoopPlaneDst of include/jsnoop_gpu.h: one destination in device memory -- component `comp` of the image listed at the same place; pitch in bytes, 0 = dense."""
+    _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("comp", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -247,6 +263,10 @@ SIGNATURES = {
     "jsnoop_coef_hist_words": (C.c_uint32, [C.POINTER(CoefHistSpec)]),
     "jsnoop_batch_pack_coef_hist": (_i, [_p, C.POINTER(CoefHistSpec), _PI, _PI, _i, _p, C.c_uint64]),
     "jsnoop_batch_read_coef_hist": (_i, [_p, C.POINTER(CoefHistSpec), _PI, _PI, _i, _p]),
+    "jsnoop_plane_spec_defaults": (None, [C.POINTER(PlaneSpec)]),
+    "jsnoop_batch_plane_size": (_i, [_p, C.POINTER(PlaneSpec), _i, _i, _PU, _PU]),
+    "jsnoop_batch_plane_bytes": (C.c_uint64, [_p, C.POINTER(PlaneSpec), _i, _i]),
+    "jsnoop_batch_pack_planes": (_i, [_p, C.POINTER(PlaneSpec), _PI, _i, C.POINTER(PlaneDst)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

@@ -262,6 +262,11 @@ public:
     // natural index 0 (jsnoop_batch_pack_coefs: one launch for the whole list, same ordering; jsnoop_coef_spec_defaults fills a spec)
     bool     BatchPackCoefs(const JsnoopCoefSpec& spec, const std::vector<int>& files, const std::vector<JsnoopCoefDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_coefs(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    // the retained Y / Cb / Cr planes of the listed files, one two-dimensional destination per (file, dst[k].comp): cropped to the SOF dimensions or decimated to the
+    // component's own grid, int16 / uint8 / float32 (jsnoop_batch_pack_planes: one launch for the whole list, same ordering; jsnoop_plane_spec_defaults fills a spec)
+    bool     BatchPackPlanes(const JsnoopPlaneSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPlaneDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack_planes(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    bool     BatchPlaneSize(const JsnoopPlaneSpec& spec, int nFileInd, int nComp, unsigned& nW, unsigned& nH) const { return jsnoop_batch_plane_size(m_b, &spec, nFileInd, nComp, &nW, &nH) == 0; }
     // the bHistoEn (bHistoEn = false: only bStatClipEn) statistics of the listed files, one row of JSNOOP_STATS_WORDS words each at pDst + k * nRowPitchWords (0 = dense)
     // in the caller's device memory, from the retained planes (jsnoop_batch_pack_stats: two launches for the whole list, same ordering; pTotals: NULL or [n][6])
     bool     BatchPackStats(bool bHistoEn, const std::vector<int>& files, void* pDst, uint64_t nRowPitchWords = 0, uint32_t* pTotals = nullptr)

@@ -135,6 +135,7 @@ struct JsnoopBatch {
     int  pack_coef_hist(const JsnoopCoefHistSpec* spec, const int* images, const int* comps, int n, void* dst, uint64_t row_pitch_words);   // jsnoop_coef_hist.cpp; the same block and event
     int  read_coef_hist(const JsnoopCoefHistSpec* spec, const int* images, const int* comps, int n, uint32_t* host_dst);   // ... into batch-owned device scratch, one D2H, one wait
     uint8_t* d_chist_rows = nullptr; size_t d_chist_rows_cap = 0; // read_coef_hist: the rows on their way to the host
+    int  pack_planes(const JsnoopPlaneSpec* spec, const int* images, int n, const JsnoopPlaneDst* dst);   // jsnoop_planes.cpp; the same block and event
     int  pack_block(size_t total);               // h_pack ready to be rewritten and at least `total` bytes large
     int  pack_send(size_t total);                // h_pack -> d_pack on the batch stream, ev_pack behind the copy
     JsDeviceArenas dev; JsArenaCaps cap;

@@ -105,3 +105,7 @@ int  js_launch_stats_batch(hipStream_t st, const int16_t* planes, const JsStatRe
 // 0, -1 on a launch error or an unknown order / range.
 int  js_launch_coef_hist(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsCoefHistRec* recs, const uint64_t* unit_base, uint32_t nrec, uint64_t total_units,
                          int order /*JSNOOP_COEF_NATURAL / _ZIGZAG*/, uint32_t range /*1 .. 127*/, void* dst, uint64_t pitch_words);
+// k_pack_planes (jsnoop_planes.hip): the retained planes of a decoded batch -> caller-owned device memory, one tensor per listed component, ONE launch for the whole list.
+// recs / unit_base: JsPlaneRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown dtype.
+int  js_launch_pack_planes(hipStream_t st, const int16_t* planes, const JsPlaneRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                           int dtype /*JSNOOP_PLANE_I16 / _U8 / _F32*/, const JsPlaneArgs& a);

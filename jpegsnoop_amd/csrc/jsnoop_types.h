@@ -174,6 +174,13 @@ struct JsStatRec { uint64_t dst, plane_off, psz, row_base; uint32_t img_x, img_y
 #define JS_COEF_HIST_WAVES 8u        /* waves of a workgroup: they share one histogram in LDS and deal the units of a share among themselves */
 #define JS_COEF_HIST_WG_PER_CU 2u    /* workgroups per compute unit: sixteen waves, four a SIMD at 128 VGPRs; two histograms of up to 65 280 bytes fit the 160 KiB of LDS */
 struct JsCoefHistRec { uint64_t dst, coef_off; uint32_t nblk, hv, first, bpm, hv_magic, pad0, pad1, pad2; uint32_t recip[64]; };
+// jsnoop_batch_pack_planes (k_pack_planes, jsnoop_planes.hip): one record per listed destination -- one component of one image, everything the kernel needs of it
+// resolved on the host -- and a prefix table in which destination k owns h * ceil(w / JS_PLANE_SEG) units: a unit is a segment of up to JS_PLANE_SEG elements of
+// one OUTPUT row, the work of one wave at a time (a lane owns eight consecutive elements).  Output element (x, y) is sample src_off + (y * ev) * pw + x * eh of
+// the plane arena; FULL is eh = ev = 1 with w x h = dim_x x dim_y.  xlim = the first source column the kernel must not read (dim_x).
+#define JS_PLANE_SEG 512u            /* output elements per unit: one (eh = 1) or two (eh = 2) 16-byte loads per lane */
+struct JsPlaneRec { uint64_t ptr, row_pitch, src_off; uint32_t pw, w, h, eh, ev, xlim, comp, segs; };   // row_pitch in bytes, resolved (never 0); src_off in samples; segs = ceil(w / JS_PLANE_SEG)
+struct JsPlaneArgs { float scale[3], bias[3]; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

@@ -520,6 +520,135 @@ class JpegBatch:
         self.sync()                              # waits for the batch's stream alone
         return result
 
+    def _plane_spec(self, torch, native, dtype, scale, bias, what):
+        if dtype is None:
+            dtype = torch.int16
+        codes = {torch.int16: capi.PLANE_I16, torch.uint8: capi.PLANE_U8, torch.float32: capi.PLANE_F32}
+        if dtype not in codes:
+            raise ValueError(f"{what}: dtype must be torch.int16, torch.uint8 or torch.float32")
+        if dtype != torch.float32 and (scale is not None or bias is not None):
+            raise ValueError(f"{what}: scale / bias belong to dtype=torch.float32")
+        spec = capi.PlaneSpec()
+        self._lib.jsnoop_plane_spec_defaults(C.byref(spec))
+        spec.res = capi.PLANE_NATIVE if native else capi.PLANE_FULL
+        spec.dtype = codes[dtype]
+        for name, v in (("scale", scale), ("bias", bias)):
+            if v is None:
+                continue
+            vals = [float(v)] * 3 if np.isscalar(v) else [float(x) for x in v]
+            if len(vals) != 3:
+                raise ValueError(f"{what}: {name} must be a number or three, one per component")
+            for c in range(3):
+                getattr(spec, name)[c] = vals[c]
+        return spec, dtype
+
+    def plane_size(self, i, comp, native=False):
+        """(h, w) of component comp (0 = Y) of image i as planes_to_torch gives it: the SOF dimensions, or with native=True the component's own
+        grid, ceil(dim / replication factor) each way (jsnoop_batch_plane_size)."""
+        spec = capi.PlaneSpec()
+        self._lib.jsnoop_plane_spec_defaults(C.byref(spec))
+        spec.res = capi.PLANE_NATIVE if native else capi.PLANE_FULL
+        w, h = C.c_uint(), C.c_uint()
+        self._chk(self._lib.jsnoop_batch_plane_size(self._h, C.byref(spec), int(i), int(comp), C.byref(w), C.byref(h)), "batch_plane_size")
+        return int(h.value), int(w.value)
+
+    def planes_to_torch(self, images=None, comps=None, native=False, dtype=None, scale=None, bias=None, stack=False, out=None):
+        """The retained Y / Cb / Cr planes of the decoded images (want_planes) as torch tensors on the batch's device, filled by ONE
+        jsnoop_batch_pack_planes -- no sample crosses PCIe.  Returns, per listed image, a list with one [h, w] tensor per component.
+
+        images: indices into the batch, any order (None = all).  comps: the components wanted of every image, counted from 0 = Y (None = all
+        the image has).  native=False: every plane cropped to the SOF dimensions, chroma replicated as the decode left it; native=True: every
+        component on its own grid, (h, w) = plane_size(i, comp, native=True) -- 4:2:0 as three planes.  dtype: torch.int16 (default: the
+        plane's samples, three fractional bits, un-clamped), torch.uint8 (min(max((v + 1024) / 8, 0), 255), the 8-bit sample the colour
+        conversion starts from) or torch.float32 (float(v) * scale[comp] + bias[comp]; scale / bias a number or three, defaults 1 and 0; one
+        rounded multiply, then one rounded add).  stack=True: one [N, C, H, W] tensor (ValueError naming the first plane whose shape
+        differs).  out=: a list (per image) of lists (per component) of tensors of exactly these shapes -- or with stack=True one
+        [N, C, H, W] tensor -- on the batch's device, of the dtype asked for, rows contiguous (the outer dimensions may be strided);
+        returned as it is.
+
+        Calls sync() first (damaged files arrive repaired; the call never decodes again), synchronises torch's current stream before the
+        launch unless the batch runs on it, and waits for the batch's stream before it returns: the tensors are ready."""
+        import torch
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"planes_to_torch: image index {i} out of range, the batch holds {n_all}")
+        spec, dtype = self._plane_spec(torch, native, dtype, scale, bias, "planes_to_torch")
+        elem = {torch.int16: 2, torch.uint8: 1, torch.float32: 4}[dtype]
+        self.sync()
+        dev = torch.device("cuda", self.device())
+        want, per_image = [], []                     # (image, component, shape) of every destination, in the order of the result; destinations per listed image
+        for i in idx:
+            ncomp = self.info(i)["ncomp"]
+            cs = list(range(ncomp)) if comps is None else [int(c) for c in comps]
+            per_image.append(len(cs))
+            for c in cs:
+                if not 0 <= c < ncomp:
+                    raise IndexError(f"planes_to_torch: component {c} of image {i}, which has {ncomp}")
+                want.append((i, c, self.plane_size(i, c, native)))
+        if stack:
+            for i, c, shp in want:
+                if shp != want[0][2]:
+                    raise ValueError(f"planes_to_torch: stack=True, but component {c} of image {i} is {shp[0]} x {shp[1]} and component {want[0][1]} of "
+                                     f"image {want[0][0]} is {want[0][2][0]} x {want[0][2][1]}")
+            if len(set(per_image)) > 1:
+                k = next(k for k, m in enumerate(per_image) if m != per_image[0])
+                raise ValueError(f"planes_to_torch: stack=True, but image {idx[k]} gives {per_image[k]} planes and image {idx[0]} gives {per_image[0]}")
+            full = (len(idx), per_image[0] if per_image else 0) + (want[0][2] if want else (0, 0))
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or tuple(out.shape) != full:
+                    raise ValueError(f"planes_to_torch: out must be a tensor of shape {list(full)}")
+                result = out
+            else:
+                result = torch.empty(full, dtype=dtype, device=dev)
+            views = [result[k][j] for k in range(full[0]) for j in range(full[1])]
+        elif out is not None:
+            rows = [list(r) for r in out]
+            if len(rows) != len(idx) or [len(r) for r in rows] != per_image:
+                raise ValueError(f"planes_to_torch: out must hold {len(idx)} lists of {per_image} tensors")
+            views, result = [t for r in rows for t in r], out
+            for k, t in enumerate(views):
+                i, c, shp = want[k]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shp:
+                    raise ValueError(f"planes_to_torch: out for component {c} of image {i} must be a tensor of shape {list(shp)}")
+        else:
+            # every plane starts at a multiple of 16 bytes of one allocation
+            sizes = [-(-(shp[0] * shp[1] * elem) // 16) * 16 // elem for _, _, shp in want]
+            flat = torch.empty(sum(sizes), dtype=dtype, device=dev)
+            views, off = [], 0
+            for (_, _, shp), sz in zip(want, sizes):
+                views.append(flat[off:off + shp[0] * shp[1]].view(shp))
+                off += sz
+            result, k = [], 0
+            for m in per_image:
+                result.append(views[k:k + m])
+                k += m
+        if out is not None:
+            for k, t in enumerate(views):
+                i, c, _ = want[k]
+                if t.device != dev:
+                    raise ValueError(f"planes_to_torch: out for component {c} of image {i} is on {t.device}, the batch on {dev}")
+                if t.dtype != dtype:
+                    raise ValueError(f"planes_to_torch: out for component {c} of image {i} is {t.dtype}, asked for {dtype}")
+        if not want:
+            return result
+        dst = (capi.PlaneDst * len(want))()
+        for k, t in enumerate(views):
+            st, shp = t.stride(), want[k][2]
+            if not (st[1] == 1 and st[0] >= shp[1]) and t.numel():
+                raise ValueError(f"planes_to_torch: destination {k}: the rows must be contiguous (strides {st})")
+            dst[k].ptr = t.data_ptr()
+            dst[k].row_pitch = st[0] * elem
+            dst[k].comp, dst[k].reserved = want[k][1], 0
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        ind = (C.c_int * len(want))(*[w[0] for w in want])
+        self._chk(self._lib.jsnoop_batch_pack_planes(self._h, C.byref(spec), ind, len(want), dst), "batch_pack_planes")
+        self.sync()                              # waits for the batch's stream alone
+        return result
+
     def stats_to_torch(self, images=None, histo_en=True, out=None, totals=False):
         """The bHistoEn (histo_en=False: only bStatClipEn) colour statistics of the decoded images as ONE int32 [n, 2482] tensor on the batch's
         device: row k is what color_stats(images[k], histo_en) returns (view it with stats_fields), computed from the retained planes by one
@@ -829,6 +958,17 @@ class JobFileResult:
         if self.batch is None:
             raise RuntimeError("stats_to_torch: this result holds no resident image (status %s)" % self.status)
         return self.batch.stats_to_torch(images=[self.image], **kw)
+
+    def planes_to_torch(self, **kw):
+        """JpegBatch.planes_to_torch for this file alone: a list with one [h, w] tensor per component (with stack=True the [1, C, H, W] tensor).  The
+        job needs want_planes.  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("planes_to_torch: this result holds no resident image (status %s)" % self.status)
+        out = kw.pop("out", None)
+        if kw.get("stack"):
+            return self.batch.planes_to_torch(images=[self.image], out=out, **kw)
+        r = self.batch.planes_to_torch(images=[self.image], out=None if out is None else [out], **kw)
+        return r[0]
 
     def coef_hist_to_torch(self, **kw):
         """JpegBatch.coef_hist_to_torch for this file alone: (pairs, rows), one row per component (comps= picks some).  Valid inside the callback, or
