@@ -589,6 +589,60 @@ int          jsnoop_batch_plane_size(const JsnoopBatch*, const JsnoopPlaneSpec*,
 uint64_t     jsnoop_batch_plane_bytes(const JsnoopBatch*, const JsnoopPlaneSpec*, int i, int comp);                           /* dense size; 0 = bad argument */
 int          jsnoop_batch_pack_planes(JsnoopBatch*, const JsnoopPlaneSpec*, const int* images, int n, const JsnoopPlaneDst* dst);
 
+/* ---- export: a decoded batch written back as baseline JPEG files, entropy-coded on the device -------------------------------------------
+ * The one product of a decode that is a FILE.  jsnoop_batch_export_jpeg encodes what the batch holds for every listed image -- the
+ * coefficient arena and the cumulative DC, so the repaired blocks of a damaged file after jsnoop_batch_sync, the merged scans of a
+ * progressive one -- as one sequential Huffman file per image (SOF0, or SOF1 where a multiplier needs 16 bits) with the Annex K tables, into
+ * device memory the batch owns.  tests/export_model.py is the definition, byte for byte; DESIGN.md section 4.13 has the contract.
+ *
+ * Levels.  AC: level = arena[b][n] / q_c[n], C division, q_c the multipliers of jsnoop_batch_image_dqt.  DC: d = (int16)(dccum[b] - dccum[p]),
+ * p the block of the same component before b in decode order (0 for the component's first block), level = d / q_c[0].  No restart markers
+ * are written.  The result word of an image:
+ *   JSNOOP_EXPORT_OK          the file was written.
+ *   JSNOOP_EXPORT_INEXACT     a value leaves a remainder (its int16 product wrapped in the decode).
+ *   JSNOOP_EXPORT_UNCODABLE   a DC difference level beyond +-2047 or an AC level beyond +-1023: Annex K has no code for it.
+ *   JSNOOP_EXPORT_UNSUPPORTED the SOF precision is not 8 (host arithmetic; nothing is launched for the image).
+ * The result is the largest of the image's blocks'; `detail` is the lowest block (counted inside the image, decode order) that has it, for
+ * INEXACT and UNCODABLE.  An image that is not OK has length 0 and disturbs no other image of the call.
+ *
+ * The file: SOI; APP0 JFIF 1.01 (units 0, density 1 x 1, no thumbnail) unless spec.jfif == 0; one DQT per component (id = component index,
+ * Pq = 1 when a multiplier is above 255); SOF0 / SOF1 (P 8, Y = dim_y, X = dim_x, ids 1..n, the image's H and V -- a one-component image
+ * 1 x 1 --, Tq = component index); DHT DC0, AC0 and for three components DC1, AC1 (Annex K.3 - K.6, one table per segment); SOS (first component
+ * tables 0/0, the others 1/1, Ss 0, Se 63, Ah/Al 0); the blocks of the MCU-padded grid in decode order (Annex F: ZRL for runs above 15,
+ * EOB unless position 63 is non-zero; MSB first; the last byte padded with ones; every FF followed by 00, a padded last byte too); EOI.
+ *
+ * Ordering and waits.  The call encodes what the arena holds when it is made, on the batch's stream behind the decode enqueued last; behind
+ * a DC-only fast-form decode the batch is first decoded once more in the generic form (jsnoop_batch_last_form goes 2 -> 1, as for
+ * jsnoop_batch_pack_coefs); a decode_ac = 0 batch exports DC-only blocks.  File sizes depend on the data, so the call waits for the device
+ * twice: once behind the measuring pass and its prefix sums (result words and bit lengths come back, the memory is sized), once at the
+ * end (file lengths come back).  When it returns 0 every file is complete.  The files stay valid until the next export, clear, upload or
+ * destroy of the batch.  -1 + jsnoop_last_error(): a NULL batch or one not decoded, an image index out of range, n < 0, a bad struct_size
+ * (read like JsnoopPackSpec's), a device error.  images == NULL means images 0 .. n - 1; any order, subsets and repeats are allowed.
+ *
+ * jsnoop_batch_export_count: entries of the last export (0: none, or invalidated).  jsnoop_batch_export_file: entry k -- device pointer
+ * (NULL when len is 0), length, result, detail, image index; any output pointer may be NULL.  jsnoop_batch_read_export: entry k to the host
+ * (waits); jsnoop_batch_export_copy: entry k device-to-device on the batch's stream into caller memory, exactly len bytes, not waited for;
+ * both refuse cap < len and return the length otherwise (0 for an entry that is not OK), -1 on error.
+ * jsnoop_export_jpeg: the single-image call beside jsnoop_export_tiff: the image a decoder holds, to a file; an image that is not OK
+ * writes no file and returns -1 with the reason.                                                                                        */
+#define JSNOOP_EXPORT_OK          0
+#define JSNOOP_EXPORT_INEXACT     1
+#define JSNOOP_EXPORT_UNCODABLE   2
+#define JSNOOP_EXPORT_UNSUPPORTED 3
+/* units of work of the export kernels (jsnoop_export.hip), for tests that place block counts and stream lengths at their seams */
+#define JSNOOP_EXPORT_TILE   256u      /* blocks of one image a workgroup measures, and later writes the bits of, at a time */
+#define JSNOOP_EXPORT_SCAN   256u      /* tiles (or stuffing chunks) of one image a prefix-sum step covers */
+#define JSNOOP_EXPORT_CHUNK  4096u     /* bytes of the un-stuffed stream a workgroup stuffs at a time */
+#define JSNOOP_EXPORT_WINDOW 8192u     /* bytes of LDS in which a workgroup assembles its bit range; what does not fit goes to memory bit group by bit group */
+typedef struct JsnoopExportSpec { uint32_t struct_size; int32_t jfif; } JsnoopExportSpec;
+void         jsnoop_export_spec_defaults(JsnoopExportSpec* out);                               /* jfif 1; NULL tolerated */
+int          jsnoop_batch_export_jpeg(JsnoopBatch*, const JsnoopExportSpec*, const int* images, int n);
+int          jsnoop_batch_export_count(const JsnoopBatch*);
+int          jsnoop_batch_export_file(const JsnoopBatch*, int k, const void** dev_ptr, uint64_t* len, int* result, uint32_t* detail, int* image);
+int64_t      jsnoop_batch_read_export(JsnoopBatch*, int k, void* host_dst, uint64_t cap);
+int64_t      jsnoop_batch_export_copy(JsnoopBatch*, int k, void* dev_dst, uint64_t cap);
+int          jsnoop_export_jpeg(JsnoopDecoder*, const char* path);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

@@ -127,6 +127,18 @@ class PlaneDst(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("row_pitch", C.c_uint64), ("comp", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+EXPORT_OK, EXPORT_INEXACT, EXPORT_UNCODABLE, EXPORT_UNSUPPORTED = 0, 1, 2, 3
+EXPORT_TILE = 256       # JSNOOP_EXPORT_TILE of include/jsnoop_gpu.h: blocks of one image a workgroup measures, and writes the bits of, at a time
+EXPORT_SCAN = 256       # JSNOOP_EXPORT_SCAN: tiles (or stuffing chunks) of one image a prefix-sum step covers
+EXPORT_CHUNK = 4096     # JSNOOP_EXPORT_CHUNK: bytes of the un-stuffed stream a workgroup stuffs at a time
+EXPORT_WINDOW = 8192    # JSNOOP_EXPORT_WINDOW: bytes of LDS in which a workgroup assembles its bit range
+
+
+class ExportSpec(C.Structure):
+    """JsnoopExportSpec of include/jsnoop_gpu.h: what jsnoop_batch_export_jpeg writes besides the image (the APP0 JFIF segment or none)."""
+    _fields_ = [("struct_size", C.c_uint32), ("jfif", C.c_int32)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -267,6 +279,13 @@ SIGNATURES = {
     "jsnoop_batch_plane_size": (_i, [_p, C.POINTER(PlaneSpec), _i, _i, _PU, _PU]),
     "jsnoop_batch_plane_bytes": (C.c_uint64, [_p, C.POINTER(PlaneSpec), _i, _i]),
     "jsnoop_batch_pack_planes": (_i, [_p, C.POINTER(PlaneSpec), _PI, _i, C.POINTER(PlaneDst)]),
+    "jsnoop_export_spec_defaults": (None, [C.POINTER(ExportSpec)]),
+    "jsnoop_batch_export_jpeg": (_i, [_p, C.POINTER(ExportSpec), _PI, _i]),
+    "jsnoop_batch_export_count": (_i, [_p]),
+    "jsnoop_batch_export_file": (_i, [_p, _i, C.POINTER(_p), C.POINTER(C.c_uint64), _PI, C.POINTER(C.c_uint32), _PI]),
+    "jsnoop_batch_read_export": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_batch_export_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_export_jpeg": (_i, [_p, C.c_char_p]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

@@ -132,6 +132,7 @@ public:
     void GetColorStats(uint32_t* pStats) { jsnoop_get_color_stats(m_h, pStats); }
     // Export to TIFF (CJPEGsnoopDoc::OnToolsExporttiff + FileTiff::WriteFile): nMode 0 RGB8, 1 RGB16, 2 YCC8
     bool ExportTiff(const std::string& strFnameOut, int nMode) { return jsnoop_export_tiff(m_h, strFnameOut.c_str(), nMode) == 0; }
+    bool ExportJpeg(const std::string& strFnameOut) { return jsnoop_export_jpeg(m_h, strFnameOut.c_str()) == 0; }   // the coefficients the decoder holds as a baseline JPEG file, coded on the device
     // hover helpers next to LookupFilePosMcu (source/JPEGsnoopViewImg.cpp:294-334); CPoint is a pair of unsigned here
     void PixelToMcu(unsigned nPixX, unsigned nPixY, unsigned& nMcuX, unsigned& nMcuY) { jsnoop_pixel_to_mcu(m_h, nPixX, nPixY, &nMcuX, &nMcuY); }               // :5056
     void PixelToBlk(unsigned nPixX, unsigned nPixY, unsigned& nBlkX, unsigned& nBlkY) { jsnoop_pixel_to_blk(m_h, nPixX, nPixY, &nBlkX, &nBlkY); }               // :5071
@@ -266,6 +267,15 @@ public:
     // component's own grid, int16 / uint8 / float32 (jsnoop_batch_pack_planes: one launch for the whole list, same ordering; jsnoop_plane_spec_defaults fills a spec)
     bool     BatchPackPlanes(const JsnoopPlaneSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPlaneDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_planes(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    // the listed files (empty list: all) written back as baseline JPEG files, entropy-coded on the device into memory the batch owns (jsnoop_batch_export_jpeg: waits twice;
+    // valid until the next export, clear, upload or destroy); entry k through BatchExportFile / BatchReadExport (false where the image could not be exported: nResult says why)
+    bool     BatchExportJpeg(const std::vector<int>& files = {}, bool bJfif = true)
+    { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;
+      return jsnoop_batch_export_jpeg(m_b, &spec, files.empty() ? nullptr : files.data(), files.empty() ? jsnoop_batch_count(m_b) : (int)files.size()) == 0; }
+    int      BatchExportCount() const { return jsnoop_batch_export_count(m_b); }
+    bool     BatchExportFile(int k, const void*& pDev, uint64_t& nLen, int& nResult, uint32_t& nDetail, int& nFileInd) const { return jsnoop_batch_export_file(m_b, k, &pDev, &nLen, &nResult, &nDetail, &nFileInd) == 0; }
+    bool     BatchReadExport(int k, std::vector<uint8_t>& file)
+    { uint64_t n = 0; if (jsnoop_batch_export_file(m_b, k, nullptr, &n, nullptr, nullptr, nullptr) || !n) return false; file.resize((size_t)n); return jsnoop_batch_read_export(m_b, k, file.data(), n) == (int64_t)n; }
     bool     BatchPlaneSize(const JsnoopPlaneSpec& spec, int nFileInd, int nComp, unsigned& nW, unsigned& nH) const { return jsnoop_batch_plane_size(m_b, &spec, nFileInd, nComp, &nW, &nH) == 0; }
     // the bHistoEn (bHistoEn = false: only bStatClipEn) statistics of the listed files, one row of JSNOOP_STATS_WORDS words each at pDst + k * nRowPitchWords (0 = dense)
     // in the caller's device memory, from the retained planes (jsnoop_batch_pack_stats: two launches for the whole list, same ordering; pTotals: NULL or [n][6])

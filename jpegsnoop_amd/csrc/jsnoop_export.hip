@@ -1,0 +1,319 @@
+// jsnoop_export.hip -- the kernels of jsnoop_batch_export_jpeg: the coefficient arena and the cumulative DC of a decoded batch entropy-coded as baseline JPEG
+// files (the definition: tests/export_model.py; host side: jsnoop_export.cpp, jsnoop_export_check.h).
+//
+// A unit is a tile of up to JS_EXPORT_TILE blocks of one listed entry, consecutive in the arena (decode order IS arena order), the work of one workgroup of
+// 256 threads: a thread owns a block.  Units never straddle two entries; the entry of a unit comes from a prefix table by one search.
+//
+//   k_export_measure  stages the tile in LDS (16-byte loads of whole 128-byte rows, written in ZIG-ZAG order; rows 132 bytes apart, so the per-thread walks below
+//                     read 32 different banks).  A thread walks its block two positions a dword -- a zero dword is two more of the run, and most are zero --,
+//                     divides, tests remainders and ranges, sums code and value bits: one bit length per block (uint16: a block has at most 20 + 63 * 26 bits),
+//                     one sum per unit, and per entry the result word (atomicMax) and the lowest offending block per kind (atomicMin).
+//   k_export_scan     exclusive prefix sums inside every entry, one workgroup per entry walking its units JS_EXPORT_SCAN at a time with a 64-bit carry;
+//                     used a second time for the FF counts of the stuffing chunks.
+//   k_export_bits     the same walk (ONE function, ex_walk, with a sink that either counts or writes), now writing: a workgroup owns the contiguous bit range of
+//                     its unit, assembles it in a JS_EXPORT_WINDOW-byte LDS window by LDS atomic OR, stores the interior words coalesced and ORs the first
+//                     and the last word, which neighbours share, into zeroed memory.  Bit groups past the window go to memory one atomic OR each: the run
+//                     length does not assume the typical block (a tile of worst-case blocks has 52 KiB of bits).
+//   k_export_ffcount  FF bytes of every JS_EXPORT_CHUNK-byte chunk of the un-stuffed streams.
+//   k_export_stuff    per chunk: an exclusive sum of the FF counts of 16-byte pieces, the stuffed bytes assembled in LDS, written out byte-coalesced at the
+//                     file's place; the first chunk's workgroup also copies the header the host built, the last one writes EOI and the file length.
+// Words of the bit stream are kept MSB-first as numbers and byte-swapped when they leave for memory.
+#include <hip/hip_runtime.h>
+#include "../../include/jsnoop_gpu.h"
+#include "jsnoop_launch.h"
+
+#define EX_THREADS 256
+#define EX_ROW_HALVES 66u                             /* 132 bytes: 33 dwords */
+#define EX_WIN_WORDS (JS_EXPORT_WINDOW / 4u)
+static_assert(JS_EXPORT_TILE == EX_THREADS && JS_EXPORT_SCAN == EX_THREADS && JS_EXPORT_CHUNK == EX_THREADS * 16u, "a thread owns a block / a unit / 16 bytes");
+
+typedef uint32_t ex_u32x4 __attribute__((ext_vector_type(4)));
+__constant__ uint8_t c_ex_zigzag[64] = JS_ZIGZAG_NATURAL;
+__constant__ uint8_t c_ex_zzpos[64] = JS_ZIGZAG_POSITION;
+
+// the last k with base[k] <= u (base[0] = 0, base[n] > u)
+__device__ __forceinline__ uint32_t ex_find(const uint32_t* __restrict__ base, uint32_t n, uint32_t u)
+{
+    uint32_t k = 0;
+    for (uint32_t top = n; top - k > 1u; ) { const uint32_t mid = (k + top) >> 1; if (base[mid] <= u) k = mid; else top = mid; }
+    return k;
+}
+// exclusive prefix sum over the workgroup; *total = the sum.  s: EX_THREADS words of LDS (free to reuse behind the call).
+__device__ __forceinline__ uint32_t ex_scan(uint32_t v, uint32_t* s, uint32_t* total)
+{
+    const uint32_t t = threadIdx.x;
+    s[t] = v; __syncthreads();
+    for (uint32_t d = 1; d < EX_THREADS; d <<= 1) {
+        const uint32_t a = t >= d ? s[t - d] : 0u; __syncthreads();
+        s[t] += a; __syncthreads();
+    }
+    const uint32_t incl = s[t]; *total = s[EX_THREADS - 1]; __syncthreads();
+    return incl - v;
+}
+
+struct ExCount { uint32_t bits = 0; __device__ __forceinline__ void put(uint32_t, uint32_t n) { bits += n; } };
+// writes bit groups of at most 27 bits at a running position: into the LDS window where the word lies inside it, else into memory
+struct ExEmit {
+    uint32_t* win; uint32_t* mem; uint64_t w0, pos;
+    __device__ __forceinline__ void word(uint64_t w, uint32_t v) {
+        if (!v) return;
+        const uint64_t rel = w - w0;
+        if (rel < EX_WIN_WORDS) atomicOr(win + (uint32_t)rel, v); else atomicOr(mem + w, __builtin_bswap32(v));
+    }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t n) {
+        const uint32_t off = (uint32_t)pos & 31u; const uint64_t w = pos >> 5;
+        if (off + n <= 32u) word(w, v << (32u - off - n));
+        else { const uint32_t k = off + n - 32u; word(w, v >> k); word(w + 1u, v << (32u - k)); }
+        pos += n;
+    }
+};
+
+// One AC value of a block: nothing but a longer run where its level is 0, else the ZRLs the run needs and the symbol (run, category) with the value bits
+template <class SINK>
+__device__ __forceinline__ void ex_coef(int32_t v, int32_t qz, uint32_t& run, bool& inexact, bool& uncodable, const uint32_t* ac, SINK& sink)
+{
+    if (!v) { run++; return; }
+    int32_t lv = 0;
+    if (qz) { lv = v / qz; inexact |= lv * qz != v; } else inexact = true;
+    if (!lv) { run++; return; }                                                     // (|v| < q: inexact, and no symbol)
+    const uint32_t a = (uint32_t)(lv < 0 ? -lv : lv), cat = 32u - (uint32_t)__clz((int)a);
+    uncodable |= a > 1023u;
+    while (run > 15u) { const uint32_t e = ac[0xF0]; sink.put(e & 0xFFFFu, e >> 16); run -= 16u; }
+    const uint32_t e = ac[((run << 4) | cat) & 255u], bits = (uint32_t)(lv < 0 ? lv - 1 : lv) & ((1u << cat) - 1u);
+    sink.put(((e & 0xFFFFu) << cat) | bits, (e >> 16) + cat);
+    run = 0;
+}
+// One block: Annex F symbols of the DC difference level and the AC levels through `sink`.  row: the block's 64 int16 in LDS in ZIG-ZAG order (ex_stage put them so),
+// read two positions a dword, a zero dword being two more of the run; q: the component's multipliers, zig-zag order; dc / ac: (length << 16 | code) by symbol.
+// Returns the block's result (JSNOOP_EXPORT_OK / _INEXACT / _UNCODABLE).
+template <class SINK>
+__device__ __forceinline__ uint32_t ex_walk(const uint16_t* row, int32_t d, const uint16_t* q, const uint32_t* dc, const uint32_t* ac, SINK& sink)
+{
+    bool inexact = false, uncodable = false;
+    {
+        const int32_t q0 = q[0]; int32_t lv = 0;
+        if (q0) { lv = d / q0; inexact |= lv * q0 != d; } else inexact |= d != 0;
+        const uint32_t a = (uint32_t)(lv < 0 ? -lv : lv), cat = 32u - (uint32_t)__clz((int)a);
+        uncodable |= a > 2047u;
+        const uint32_t e = dc[cat & 15u], bits = (uint32_t)(lv < 0 ? lv - 1 : lv) & ((1u << cat) - 1u);
+        sink.put(((e & 0xFFFFu) << cat) | bits, (e >> 16) + cat);
+    }
+    const uint32_t* row32 = reinterpret_cast<const uint32_t*>(row);                    // (a row starts on a multiple of 132 bytes)
+    uint32_t run = 0;
+    ex_coef((int32_t)row32[0] >> 16, q[1], run, inexact, uncodable, ac, sink);          // position 1; position 0, the arena's slot 0, is not read
+    for (uint32_t w = 1; w < 32u; w++) {
+        const uint32_t two = row32[w];
+        if (!two) { run += 2u; continue; }
+        ex_coef((int32_t)(int16_t)(two & 0xFFFFu), q[2u * w], run, inexact, uncodable, ac, sink);
+        ex_coef((int32_t)two >> 16, q[2u * w + 1u], run, inexact, uncodable, ac, sink);
+    }
+    if (run) { const uint32_t e = ac[0]; sink.put(e & 0xFFFFu, e >> 16); }
+    return uncodable ? JSNOOP_EXPORT_UNCODABLE : (inexact ? JSNOOP_EXPORT_INEXACT : JSNOOP_EXPORT_OK);
+}
+
+struct ExShared {
+    uint16_t rows[JS_EXPORT_TILE * EX_ROW_HALVES];
+    uint16_t q[3][64];
+    uint32_t dc[2][16], ac[2][256];
+    uint32_t scan[EX_THREADS];
+};
+// the tile's rows -- turned into zig-zag order on the way: a thread always holds the same eight natural indices, so it looks their positions up once --, the entry's
+// multipliers (zig-zag order too) and the code tables into LDS; ends with a barrier
+__device__ __forceinline__ void ex_stage(ExShared& s, const int16_t* __restrict__ coef, const JsExportRec& r, uint32_t t0, uint32_t nb, const uint32_t* __restrict__ tabs)
+{
+    const uint32_t t = threadIdx.x, ch = t & 7u;                                       // (p * EX_THREADS + t) & 7 for every p
+    const ex_u32x4* src = reinterpret_cast<const ex_u32x4*>(coef + (r.coef_off + t0) * 64u);
+    uint32_t zp[8];
+    #pragma unroll
+    for (uint32_t e = 0; e < 8u; e++) zp[e] = c_ex_zzpos[ch * 8u + e];
+    #pragma unroll
+    for (uint32_t p = 0; p < 8u; p++) {
+        const uint32_t i = p * EX_THREADS + t, blk = i >> 3;
+        if (blk < nb) {
+            const ex_u32x4 v = src[i]; uint16_t* o = s.rows + blk * EX_ROW_HALVES;
+            o[zp[0]] = (uint16_t)v.x; o[zp[1]] = (uint16_t)(v.x >> 16); o[zp[2]] = (uint16_t)v.y; o[zp[3]] = (uint16_t)(v.y >> 16);
+            o[zp[4]] = (uint16_t)v.z; o[zp[5]] = (uint16_t)(v.z >> 16); o[zp[6]] = (uint16_t)v.w; o[zp[7]] = (uint16_t)(v.w >> 16);
+        }
+    }
+    if (t < 192u) s.q[t >> 6][t & 63u] = r.q[t >> 6][c_ex_zigzag[t & 63u]];
+    if (t < 32u) s.dc[t >> 4][t & 15u] = tabs[t];
+    s.ac[0][t] = tabs[32u + t]; s.ac[1][t] = tabs[288u + t];
+    __syncthreads();
+}
+// what block j of the entry is: its component (0-based) and its DC difference
+__device__ __forceinline__ int32_t ex_dc_diff(const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ rp, uint64_t coef_off, uint32_t bpm, uint32_t j, uint32_t* comp)
+{
+    const uint32_t pos = j % bpm, back = rp->back[pos];
+    *comp = rp->comp[pos];
+    const int32_t cur = dccum[coef_off + j], prev = j >= back ? (int32_t)dccum[coef_off + j - back] : 0;
+    return (int32_t)(int16_t)(cur - prev);
+}
+
+__global__ void __launch_bounds__(EX_THREADS) k_export_measure(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
+                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs,
+                                                               uint16_t* __restrict__ blk_bits, uint32_t* __restrict__ unit_bits, uint32_t* __restrict__ res /*[nrec] result, then [nrec][2] lowest block per kind*/)
+{
+    __shared__ ExShared s;
+    __shared__ uint32_t s_red[4];                                 // sum of bits, result, lowest inexact block, lowest uncodable block
+    const uint32_t t = threadIdx.x, unit = blockIdx.x, k = ex_find(unit_base, nrec, unit);
+    const JsExportRec* rp = recs + k;
+    const uint32_t t0 = (unit - unit_base[k]) * JS_EXPORT_TILE, nblk = rp->nblk, nb = min(JS_EXPORT_TILE, nblk - t0), bpm = rp->bpm;
+    const uint64_t coef_off = rp->coef_off;
+    if (t == 0) { s_red[0] = 0u; s_red[1] = 0u; s_red[2] = 0xFFFFFFFFu; s_red[3] = 0xFFFFFFFFu; }
+    ex_stage(s, coef, *rp, t0, nb, tabs);
+    if (t < nb) {
+        const uint32_t j = t0 + t; uint32_t c;
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, &c);
+        const uint32_t tb = c ? 1u : 0u;
+        ExCount sink;
+        const uint32_t st = ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
+        blk_bits[rp->blk_base + j] = (uint16_t)sink.bits;
+        atomicAdd(&s_red[0], sink.bits);
+        if (st) { atomicMax(&s_red[1], st); atomicMin(&s_red[1u + st], j); }
+    }
+    __syncthreads();
+    if (t == 0) {
+        unit_bits[unit] = s_red[0];
+        if (s_red[1]) {
+            atomicMax(res + k, s_red[1]);
+            if (s_red[2] != 0xFFFFFFFFu) atomicMin(res + nrec + 2u * k, s_red[2]);
+            if (s_red[3] != 0xFFFFFFFFu) atomicMin(res + nrec + 2u * k + 1u, s_red[3]);
+        }
+    }
+}
+
+// off[i] = the sum of cnt[base[k] .. i) for every i of entry k; total[k] = the entry's sum
+__global__ void __launch_bounds__(EX_THREADS) k_export_scan(const uint32_t* __restrict__ cnt, uint64_t* __restrict__ off, const uint32_t* __restrict__ base, uint64_t* __restrict__ total)
+{
+    __shared__ uint32_t s[EX_THREADS];
+    const uint32_t t = threadIdx.x, k = blockIdx.x, a = base[k], e = base[k + 1];
+    uint64_t carry = 0;
+    for (uint32_t i0 = a; i0 < e; i0 += JS_EXPORT_SCAN) {           // (a, e, i0: the same in every thread -- the barriers inside ex_scan are met by all)
+        const uint32_t i = i0 + t, v = i < e && i >= i0 ? cnt[i] : 0u;
+        uint32_t step;
+        const uint32_t ex = ex_scan(v, s, &step);
+        if (i < e && i >= i0) off[i] = carry + ex;
+        carry += step;
+        if (e - i0 <= JS_EXPORT_SCAN) break;                        // (i0 + JS_EXPORT_SCAN must not wrap)
+    }
+    if (t == 0) total[k] = carry;
+}
+
+__global__ void __launch_bounds__(EX_THREADS) k_export_bits(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
+                                                            const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs,
+                                                            const uint16_t* __restrict__ blk_bits, const uint64_t* __restrict__ unit_off, uint8_t* __restrict__ ustream)
+{
+    __shared__ ExShared s;
+    __shared__ uint32_t s_win[EX_WIN_WORDS];
+    const uint32_t t = threadIdx.x, unit = blockIdx.x, k = ex_find(unit_base, nrec, unit);
+    const JsExportRec* rp = recs + k;
+    if (!rp->live) return;
+    const uint32_t t0 = (unit - unit_base[k]) * JS_EXPORT_TILE, nblk = rp->nblk, nb = min(JS_EXPORT_TILE, nblk - t0), bpm = rp->bpm;
+    const uint64_t coef_off = rp->coef_off, total_bits = rp->bits;
+    uint32_t* mem = reinterpret_cast<uint32_t*>(ustream + rp->u_off);
+    for (uint32_t i = t; i < EX_WIN_WORDS; i += EX_THREADS) s_win[i] = 0u;
+    ex_stage(s, coef, *rp, t0, nb, tabs);
+    uint32_t run_bits;
+    const uint32_t mine = t < nb ? (uint32_t)blk_bits[rp->blk_base + t0 + t] : 0u, before = ex_scan(mine, s.scan, &run_bits);
+    const uint64_t b0 = unit_off[unit];
+    uint64_t b1 = b0 + run_bits;                                    // the range this workgroup writes: [b0, b1)
+    const bool last_unit = t0 + nb == nblk;
+    const uint32_t pad = (uint32_t)(0u - total_bits) & 7u;          // ones behind the entry's last block, up to a whole byte
+    if (last_unit) b1 += pad;
+    const uint64_t w0 = b0 >> 5, wl = (b1 - 1u) >> 5;               // first and last word of the range (every block has bits: b1 > b0)
+    if (t < nb) {
+        const uint32_t j = t0 + t; uint32_t c;
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, &c);
+        const uint32_t tb = c ? 1u : 0u;
+        ExEmit sink{ s_win, mem, w0, b0 + before };
+        ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
+        if (j + 1u == nblk && pad) sink.put((1u << pad) - 1u, pad);
+    }
+    __syncthreads();
+    const uint64_t nw = wl - w0 + 1u;
+    const uint32_t in_win = nw < EX_WIN_WORDS ? (uint32_t)nw : EX_WIN_WORDS;
+    for (uint32_t i = t; i < in_win; i += EX_THREADS) {
+        const uint32_t v = __builtin_bswap32(s_win[i]);
+        if (i == 0u || w0 + i == wl) { if (v) atomicOr(mem + w0 + i, v); }      // shared with the neighbouring range
+        else mem[w0 + i] = v;
+    }
+}
+
+__device__ __forceinline__ uint32_t ex_ff16(ex_u32x4 v, uint32_t valid /*bytes that count, from the first*/)
+{
+    uint32_t n = 0; const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+    #pragma unroll
+    for (uint32_t i = 0; i < 16u; i++) n += (i < valid && ((w[i >> 2] >> ((i & 3u) * 8u)) & 255u) == 255u) ? 1u : 0u;
+    return n;
+}
+
+__global__ void __launch_bounds__(EX_THREADS) k_export_ffcount(const JsExportRec* __restrict__ recs, const uint32_t* __restrict__ chunk_base, uint32_t nrec,
+                                                               const uint8_t* __restrict__ ustream, uint32_t* __restrict__ chunk_ff)
+{
+    __shared__ uint32_t s_n;
+    const uint32_t t = threadIdx.x, chunk = blockIdx.x, k = ex_find(chunk_base, nrec, chunk);
+    const JsExportRec* rp = recs + k;
+    const uint64_t nbytes = (rp->bits + 7u) >> 3, c0 = (uint64_t)(chunk - chunk_base[k]) * JS_EXPORT_CHUNK, at = c0 + t * 16u;
+    if (t == 0) s_n = 0u;
+    __syncthreads();
+    if (at < nbytes) {
+        const ex_u32x4 v = *reinterpret_cast<const ex_u32x4*>(ustream + rp->u_off + at);
+        const uint32_t n = ex_ff16(v, (uint32_t)min((uint64_t)16u, nbytes - at));
+        if (n) atomicAdd(&s_n, n);
+    }
+    __syncthreads();
+    if (t == 0) chunk_ff[chunk] = s_n;
+}
+
+__global__ void __launch_bounds__(EX_THREADS) k_export_stuff(const JsExportRec* __restrict__ recs, const uint32_t* __restrict__ chunk_base, uint32_t nrec,
+                                                             const uint8_t* __restrict__ ustream, const uint64_t* __restrict__ chunk_off, const uint8_t* __restrict__ hdrs,
+                                                             uint8_t* __restrict__ out, uint64_t* __restrict__ len)
+{
+    __shared__ uint32_t s_scan[EX_THREADS];
+    __shared__ uint8_t s_out[2u * JS_EXPORT_CHUNK];
+    const uint32_t t = threadIdx.x, chunk = blockIdx.x, k = ex_find(chunk_base, nrec, chunk);
+    const JsExportRec* rp = recs + k;
+    const uint32_t lc = chunk - chunk_base[k], nchunks = chunk_base[k + 1] - chunk_base[k], hdr_len = rp->hdr_len;
+    const uint64_t nbytes = (rp->bits + 7u) >> 3, c0 = (uint64_t)lc * JS_EXPORT_CHUNK, at = c0 + t * 16u;
+    const uint32_t here = (uint32_t)min((uint64_t)JS_EXPORT_CHUNK, nbytes - c0);
+    uint8_t* file = out + rp->out_off;
+    ex_u32x4 v = { 0u, 0u, 0u, 0u }; uint32_t valid = 0;
+    if (at < nbytes) { v = *reinterpret_cast<const ex_u32x4*>(ustream + rp->u_off + at); valid = (uint32_t)min((uint64_t)16u, nbytes - at); }
+    uint32_t ff_here;
+    const uint32_t before = ex_scan(ex_ff16(v, valid), s_scan, &ff_here);
+    {
+        uint32_t o = t * 16u + before; const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+        #pragma unroll
+        for (uint32_t i = 0; i < 16u; i++) if (i < valid) {
+            const uint32_t b = (w[i >> 2] >> ((i & 3u) * 8u)) & 255u;
+            s_out[o++] = (uint8_t)b;
+            if (b == 255u) s_out[o++] = 0u;
+        }
+    }
+    __syncthreads();
+    uint8_t* dst = file + hdr_len + c0 + chunk_off[chunk];
+    const uint32_t n_out = here + ff_here;
+    for (uint32_t i = t; i < n_out; i += EX_THREADS) dst[i] = s_out[i];
+    if (lc == 0u) { const uint8_t* h = hdrs + rp->hdr_off; for (uint32_t i = t; i < hdr_len; i += EX_THREADS) file[i] = h[i]; }
+    if (lc + 1u == nchunks && t == 0u) { dst[n_out] = 0xFFu; dst[n_out + 1u] = 0xD9u; len[k] = (uint64_t)hdr_len + c0 + chunk_off[chunk] + n_out + 2u; }
+}
+
+int js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                             const uint32_t* tabs, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
+{
+    if (!nrec) return 0;
+    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, blk_bits, unit_bits, res);
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, unit_bits, unit_off, unit_base, ent_bits);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int js_launch_export_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
+                           uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
+                           uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
+{
+    if (!nrec || !total_units || !total_chunks) return 0;
+    hipLaunchKernelGGL(k_export_bits, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, blk_bits, unit_off, ustream);
+    hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_ff);
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, chunk_ff, chunk_off, chunk_base, ent_ff);
+    hipLaunchKernelGGL(k_export_stuff, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_off, hdrs, out, len);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}

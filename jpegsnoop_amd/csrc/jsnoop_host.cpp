@@ -305,6 +305,9 @@ JsnoopBatch::~JsnoopBatch()
     if (d_stats) hipFree(d_stats);
     if (d_stats_rows) hipFree(d_stats_rows);
     if (d_chist_rows) hipFree(d_chist_rows);
+    if (d_export_tmp) hipFree(d_export_tmp);
+    if (d_export_u) hipFree(d_export_u);
+    if (d_export_out) hipFree(d_export_out);
     if (ev_pack) hipEventDestroy(ev_pack);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     for (auto& e : ev2) if (e) hipEventDestroy(e);
@@ -322,7 +325,7 @@ int JsnoopBatch::ensure_aux()
 }
 void JsnoopBatch::clear()
 {
-    imgs.clear(); hinfo.clear(); tables.clear(); raw_bytes = 0; uploaded = false; last_form = 0; host_flags.clear(); side_done.clear(); side_mode.clear(); side_anoms.clear(); side_chunk_ok.clear(); side_events.clear(); side_pre.clear();
+    imgs.clear(); hinfo.clear(); tables.clear(); raw_bytes = 0; uploaded = false; last_form = 0; host_flags.clear(); side_done.clear(); side_mode.clear(); side_anoms.clear(); side_chunk_ok.clear(); side_events.clear(); side_pre.clear(); exports.clear();
     js_prog_clear(this);
 }
 int JsnoopBatch::reserve_pinned(size_t need)
@@ -437,6 +440,7 @@ int JsnoopBatch::upload()
     HIP_TRY(hipSetDevice(device));
     const size_t n = imgs.size();
     if (!n) { js_set_error("upload: empty batch"); return -1; }
+    exports.clear();                                              // (the files of an export describe the arena of the batch as it was)
     uint64_t blocks = 0, dibb = 0, plane = 0, side = 0, ustr = 0, subs = 0;
     std::vector<uint32_t> wg(n + 1), usb(2 * (n + 1)), syb(2 * (n + 1));       // syb: write-pass bases, then sync-pass bases; usb: 4 KiB chunks, then super-chunks of four (k_unstuff_fused)
     uint64_t segw = 0, mcub = 0, recw = 0; uint32_t usc = 0, us4 = 0, syw = 0, snw = 0;

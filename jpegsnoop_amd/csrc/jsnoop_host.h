@@ -136,6 +136,13 @@ struct JsnoopBatch {
     int  read_coef_hist(const JsnoopCoefHistSpec* spec, const int* images, const int* comps, int n, uint32_t* host_dst);   // ... into batch-owned device scratch, one D2H, one wait
     uint8_t* d_chist_rows = nullptr; size_t d_chist_rows_cap = 0; // read_coef_hist: the rows on their way to the host
     int  pack_planes(const JsnoopPlaneSpec* spec, const int* images, int n, const JsnoopPlaneDst* dst);   // jsnoop_planes.cpp; the same block and event
+    // jsnoop_batch_export_jpeg (jsnoop_export.cpp): the same block and event, two waits; the files live in d_export_out until the next export, clear, upload or destroy
+    int  export_jpeg(const JsnoopExportSpec* spec, const int* images, int n);
+    struct JsExportEntry { uint64_t off, len; int result; uint32_t detail; int image; };   // entry k of the last export: its file at d_export_out + off
+    std::vector<JsExportEntry> exports;
+    uint8_t* d_export_tmp = nullptr; size_t d_export_tmp_cap = 0; // scratch of the first phase: result words, bit lengths per block / tile / entry
+    uint8_t* d_export_u = nullptr; size_t d_export_u_cap = 0;     // the chunk tables and the un-stuffed streams of the second phase
+    uint8_t* d_export_out = nullptr; size_t d_export_out_cap = 0; // the files
     int  pack_block(size_t total);               // h_pack ready to be rewritten and at least `total` bytes large
     int  pack_send(size_t total);                // h_pack -> d_pack on the batch stream, ev_pack behind the copy
     JsDeviceArenas dev; JsArenaCaps cap;

@@ -109,3 +109,15 @@ int  js_launch_coef_hist(hipStream_t st, const int16_t* coef, const int16_t* dcc
 // recs / unit_base: JsPlaneRec and its prefix table (jsnoop_types.h), both in device memory.  0, -1 on a launch error or an unknown dtype.
 int  js_launch_pack_planes(hipStream_t st, const int16_t* planes, const JsPlaneRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                            int dtype /*JSNOOP_PLANE_I16 / _U8 / _F32*/, const JsPlaneArgs& a);
+// jsnoop_batch_export_jpeg (jsnoop_export.hip), first phase: k_export_measure over every unit, then k_export_scan over the units of every entry.
+// recs / unit_base / tabs (JS_EXPORT_TAB_WORDS words: length << 16 | code by symbol, DC0 DC1 AC0 AC1) in device memory; blk_bits: one uint16 per listed block;
+// unit_bits / unit_off: one entry per unit; res: [nrec] result words, then [nrec][2] lowest offending block (zeroed / set to all ones by the caller);
+// ent_bits: bits of every entry.  0, -1 on a launch error.
+#define JS_EXPORT_TAB_WORDS 544u
+int  js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                              const uint32_t* tabs, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits);
+// ... second phase, the records now with live / bits / u_off / out_off: k_export_bits into the zeroed un-stuffed streams, k_export_ffcount, k_export_scan over the
+// chunks of every entry, k_export_stuff into the files (hdrs: the headers the host built; len: one word per entry, zeroed by the caller).
+int  js_launch_export_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
+                            uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
+                            uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);

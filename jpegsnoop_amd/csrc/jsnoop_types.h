@@ -181,6 +181,17 @@ struct JsCoefHistRec { uint64_t dst, coef_off; uint32_t nblk, hv, first, bpm, hv
 #define JS_PLANE_SEG 512u            /* output elements per unit: one (eh = 1) or two (eh = 2) 16-byte loads per lane */
 struct JsPlaneRec { uint64_t ptr, row_pitch, src_off; uint32_t pw, w, h, eh, ev, xlim, comp, segs; };   // row_pitch in bytes, resolved (never 0); src_off in samples; segs = ceil(w / JS_PLANE_SEG)
 struct JsPlaneArgs { float scale[3], bias[3]; };
+// jsnoop_batch_export_jpeg (k_export_*, jsnoop_export.hip): one record per listed entry -- one image, everything the kernels need of it resolved on the host --
+// and prefix tables over the entries: unit_base (a unit is a tile of up to JS_EXPORT_TILE blocks of the image, consecutive in the arena, the work of one
+// workgroup; an entry that is not encoded owns none) and, in the second phase, chunk_base (a chunk is JS_EXPORT_CHUNK bytes of the entry's un-stuffed stream).
+// comp[j] / back[j]: the component of block j of an MCU, and how many blocks back the block of the same component before it lies (in the MCU, or the
+// component's last block of the MCU before); q: the multipliers by component, natural order.  Phase 2 fills live, bits, u_off, out_off, out_cap.
+#define JS_EXPORT_TILE   256u        /* public: JSNOOP_EXPORT_TILE */
+#define JS_EXPORT_SCAN   256u        /* public: JSNOOP_EXPORT_SCAN */
+#define JS_EXPORT_CHUNK  4096u       /* public: JSNOOP_EXPORT_CHUNK */
+#define JS_EXPORT_WINDOW 8192u       /* public: JSNOOP_EXPORT_WINDOW */
+struct JsExportRec { uint64_t coef_off, blk_base, bits, u_off, out_off, out_cap; uint32_t nblk, bpm, hdr_off, hdr_len, live, ncomp;
+                     uint8_t comp[JS_MAX_BLK_PER_MCU], back[JS_MAX_BLK_PER_MCU]; uint16_t q[3][64]; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

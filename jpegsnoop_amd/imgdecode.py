@@ -83,6 +83,11 @@ class CimgDecode:
     def ExportTiff(self, path: str, nMode: int = 0) -> bool:
         return self._lib.jsnoop_export_tiff(self._h, path.encode(), nMode) == 0
 
+    def export_jpeg(self, path: str) -> bool:
+        """The decoded image written back as a baseline JPEG file (jsnoop_export_jpeg): the coefficients the decoder holds, entropy-coded on the
+        device.  False, and no file, where the image cannot be exported (capi.last_error() has the reason)."""
+        return self._lib.jsnoop_export_jpeg(self._h, path.encode()) == 0
+
     # --- results ---------------------------------------------------------------------------
     def IsPreviewReady(self): return bool(self._lib.jsnoop_is_preview_ready(self._h))
     def GetImageSize(self):
@@ -827,6 +832,70 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_log(self._h, i, int(histo_en), int(stat_clip_en), int(quiet), cb, None), "batch_log")
         return out
 
+    def _export(self, images, jfif, what):
+        n_all = len(self)
+        idx = list(range(n_all)) if images is None else [int(i) for i in images]
+        for i in idx:
+            if not 0 <= i < n_all:
+                raise IndexError(f"{what}: image index {i} out of range, the batch holds {n_all}")
+        spec = capi.ExportSpec()
+        self._lib.jsnoop_export_spec_defaults(C.byref(spec))
+        spec.jfif = 1 if jfif else 0
+        self.sync()
+        ind = (C.c_int * max(len(idx), 1))(*idx)
+        self._chk(self._lib.jsnoop_batch_export_jpeg(self._h, C.byref(spec), ind, len(idx)), "batch_export_jpeg")
+        return self.export_results()
+
+    def export_results(self):
+        """The entries of the last export_jpeg / export_jpeg_to_torch, in the order of its list: dicts with image, result (capi.EXPORT_OK / _INEXACT /
+        _UNCODABLE / _UNSUPPORTED), detail (the lowest offending block of the image, decode order; 0 where the result has none), len (0 unless OK)
+        and ptr (device address of the file, 0 with len 0).  Empty after clear() / upload()."""
+        out = []
+        for k in range(self._lib.jsnoop_batch_export_count(self._h)):
+            ptr, ln, res, det, img = C.c_void_p(), C.c_uint64(), C.c_int(), C.c_uint32(), C.c_int()
+            self._chk(self._lib.jsnoop_batch_export_file(self._h, k, C.byref(ptr), C.byref(ln), C.byref(res), C.byref(det), C.byref(img)), "batch_export_file")
+            out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
+        return out
+
+    def export_jpeg(self, images=None, jfif=True):
+        """What the batch holds for the listed images (None = all; any order, repeats allowed) written back as baseline JPEG files, entropy-coded on
+        the device by ONE jsnoop_batch_export_jpeg: a list with the file's bytes per entry, None where the image could not be exported
+        (export_results() says why).  An exported file decodes to the same coefficients; where the source was a clean file, to the same pixels.
+        jfif=False leaves the APP0 segment out.  Calls sync() first (a damaged file is exported as repaired); behind a DC-only fast-form decode the
+        batch is decoded once more in the generic form."""
+        files = []
+        for k, e in enumerate(self._export(images, jfif, "export_jpeg")):
+            if not e["len"]:
+                files.append(None); continue
+            buf = (C.c_uint8 * e["len"])()
+            got = self._lib.jsnoop_batch_read_export(self._h, k, buf, e["len"])
+            if got != e["len"]:
+                raise RuntimeError(f"batch_read_export failed: {capi.last_error()}")
+            files.append(bytes(buf))
+        return files
+
+    def export_jpeg_to_torch(self, images=None, jfif=True):
+        """export_jpeg, but the files stay on the device: a list with one uint8 tensor per entry (None where the image could not be exported), copied
+        out of the batch's memory by jsnoop_batch_export_copy -- they outlive the next export."""
+        import torch
+        dev = torch.device("cuda", self.device())
+        res = self._export(images, jfif, "export_jpeg_to_torch")
+        sizes = [-(-e["len"] // 16) * 16 for e in res]
+        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        out, off = [], 0
+        for k, (e, sz) in enumerate(zip(res, sizes)):
+            if not e["len"]:
+                out.append(None); continue
+            t = flat[off:off + e["len"]]; off += sz
+            if self._lib.jsnoop_batch_export_copy(self._h, k, t.data_ptr(), e["len"]) != e["len"]:
+                raise RuntimeError(f"batch_export_copy failed: {capi.last_error()}")
+            out.append(t)
+        self.sync()
+        return out
+
     def export_tiff(self, i, path: str, mode: int = 0):
         self._chk(self._lib.jsnoop_batch_export_tiff(self._h, i, path.encode(), mode), "batch_export_tiff")
 
@@ -980,6 +1049,13 @@ class JobFileResult:
             comps = [int(c) for c in comps]
             return self.batch.coef_hist_to_torch(images=[self.image] * len(comps), comps=comps, **kw)
         return self.batch.coef_hist_to_torch(images=[self.image], **kw)
+
+    def export_jpeg(self, **kw):
+        """JpegBatch.export_jpeg for this file alone: the file's bytes, or None where the image could not be exported (batch.export_results()[0] says
+        why).  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        if self.batch is None:
+            raise RuntimeError("export_jpeg: this result holds no resident image (status %s)" % self.status)
+        return self.batch.export_jpeg(images=[self.image], **kw)[0]
 
     def __repr__(self):
         return "JobFileResult(index=%d, status=%s, kind=%s, shard=%d, round=%d)" % (self.index, self.status, self.kind, self.shard, self.round)
