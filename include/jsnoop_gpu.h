@@ -191,6 +191,9 @@ void            jsnoop_idct_block(JsnoopDecoder*, const int16_t* coef64, float* 
 /* every (Y, Cb, Cr) in [-128,127]^3 through the device ConvertYCCtoRGBFastFloat (ImgDecode.cpp:4086):
  * out_bgra[(Y+128)<<16 | (Cb+128)<<8 | (Cr+128)] = B | G<<8 | R<<16; 2^24 words; 0 on success */
 int             jsnoop_color_sweep(JsnoopDecoder*, uint32_t* out_bgra);
+/* the same sweep, same layout, through the offset form the 4:2:0 back end converts with (one evaluation per chroma
+ * sample, a pixel = saturating adds, the listed exceptions of jsnoop_color_exc.h applied) */
+int             jsnoop_color_offsets_sweep(JsnoopDecoder*, uint32_t* out_bgra);
 /* which device path decoded the last image: 1 = parallel (self-synchronising) entropy
  * decode, 2 = sequential exact-mirror entropy kernel (taken for streams the parallel
  * path flags as malformed), 0 = nothing decoded */

@@ -215,6 +215,7 @@ SIGNATURES = {
     "jsnoop_dht_lookupfast": (_p, [_p]),
     "jsnoop_idct_block": (None, [_p, _p, _p]),
     "jsnoop_color_sweep": (C.c_int, [_p, _p]),
+    "jsnoop_color_offsets_sweep": (C.c_int, [_p, _p]),
     "jsnoop_last_path": (_i, [_p]),
     "jsnoop_last_flags": (C.c_uint32, [_p]),
     "jsnoop_last_side_mode": (_i, [_p]),

@@ -1018,6 +1018,18 @@ int jsnoop_color_sweep(JsnoopDecoder* d, uint32_t* out_bgra)
     if (e != hipSuccess) { js_set_error("jsnoop_color_sweep: device error"); return -1; }
     return 0;
 }
+int jsnoop_color_offsets_sweep(JsnoopDecoder* d, uint32_t* out_bgra)
+{
+    JsnoopBatch* b = d->batch; hipSetDevice(b->device);
+    uint32_t* tmp = nullptr;
+    if (hipMalloc(&tmp, (size_t)4 << 24) != hipSuccess) { js_set_error("jsnoop_color_offsets_sweep: hipMalloc failed"); return -1; }
+    js_launch_color_offsets_sweep(b->stream, tmp);
+    hipError_t e = hipMemcpyAsync(out_bgra, tmp, (size_t)4 << 24, hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    hipFree(tmp);
+    if (e != hipSuccess) { js_set_error("jsnoop_color_offsets_sweep: device error"); return -1; }
+    return 0;
+}
 int jsnoop_last_path(JsnoopDecoder* d) { return d->last_path; }
 uint32_t jsnoop_last_flags(JsnoopDecoder* d) { return d->last_flags; }
 int jsnoop_last_side_mode(JsnoopDecoder* d)

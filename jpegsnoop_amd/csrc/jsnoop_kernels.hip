@@ -19,6 +19,7 @@
 #include "jsnoop_types.h"
 #include "jsnoop_launch.h"
 #include "jsnoop_stat_pixel.h"
+#include "jsnoop_color_exc.h"
 
 #define WAVE 64
 // wave vote on a bool: the HIP wrapper __ballot(int) makes the compiler materialise the predicate as 0 / 1 and compare it again (two
@@ -491,6 +492,69 @@ __device__ __forceinline__ uint32_t lds_r32(uint32_t a) { return *(const __attri
 __device__ __forceinline__ uint2 lds_r64(uint32_t a) { const u32x2_t v = *(const __attribute__((address_space(3))) u32x2_t*)(uintptr_t)a; return make_uint2(v.x, v.y); }
 __device__ __forceinline__ void lds_w64(uint32_t a, uint32_t x, uint32_t y) { u32x2_t v; v.x = x; v.y = y; *(__attribute__((address_space(3))) u32x2_t*)(uintptr_t)a = v; }
 
+// ---- offset form of the colour conversion (4:2:0: a chroma sample serves four pixels) ------------------------------------
+// ycc_core rounds after every operation, Y included -- and still, for every clamped triple, R = sat_u8(Y + Roff(Cr)), B = sat_u8(Y + Boff(Cb))
+// and G = sat_u8(Y + Goff(Cb, Cr)) with the offsets = the uncapped chain at Y = 0, floored: checked over all 2^24 triples against the oracle
+// by tools/gen/gen_color_offsets.py, which also writes down the exceptions (jsnoop_color_exc.h: G one lower at JS_COLOR_EXC_TRIPLES triples,
+// all in JS_COLOR_EXC_PAIRS chroma pairs, a 256-bit mask over Y + 128 each).  So the chain runs once per chroma SAMPLE (chroma_offsets) and a
+// pixel is clamp, convert, three adds of small integers (exact: no floor, no bias) and three v_cvt_pk_u8_f32 (offs_pixel).
+// tests/test_gpu_color_offsets.py runs these very functions over all 2^24 triples (k_color_offsets_sweep).
+struct ChromaOff { float r, g, b; };
+#define CO_BYTES (3u * 256u)                                     // per wave: the offsets of an MCU's 64 chroma samples as floats, a plane of r, of g and of b
+#define EXC_TAB_BYTES ((JS_COLOR_EXC_PAIRS + 1u) * 32u)          // per workgroup: row 0 = no exception, row e = mask of pair e - 1
+static_assert(JS_COLOR_EXC_PAIRS >= 1 && JS_COLOR_EXC_PAIRS <= 3, "a sample's pair is tagged in two bits");
+__device__ __constant__ uint32_t c_color_exc[JS_COLOR_EXC_PAIRS][8] = JS_COLOR_EXC_MASKS;
+// cb, cr: after >> 3 and the clamp
+__device__ __forceinline__ ChromaOff chroma_offsets(int cb, int cr)
+{
+    const float kr = 0.299f, kg = 0.587f, kb = 0.114f, rkg = 1.0f / kg;
+    const float crm = chroma_r((float)cr), cbm = chroma_b((float)cb);
+    // ycc_core at fy = 0: r = crm, b = cbm (adding 0 is exact); RN is sign-symmetric, so RN(0 - a) = -a and the first subtraction is a sign
+    const float x = __fsub_rn(-__fmul_rn(kb, cbm), __fmul_rn(kr, crm));
+    const float q0 = __fmul_rn(x, rkg);
+    const float g = __builtin_fmaf(__builtin_fmaf(-kg, q0, x), rkg, q0);          // == x / kg: one of the numerators ycc_core's proof covers
+    ChromaOff o;
+    o.r = __builtin_floorf(__fadd_rn(crm, 128.0f)); o.g = __builtin_floorf(__fadd_rn(g, 128.0f)); o.b = __builtin_floorf(__fadd_rn(cbm, 128.0f));
+    return o;
+}
+// 0: the sample is none of the listed pairs, else 1 + its index
+__device__ __forceinline__ uint32_t color_exc_index(int cb, int cr)
+{
+    const int pairs[JS_COLOR_EXC_PAIRS][2] = JS_COLOR_EXC_CBCR;
+    const int key = cb * 256 + cr;
+    uint32_t e = 0;
+    #pragma unroll
+    for (int k = 0; k < JS_COLOR_EXC_PAIRS; k++) e = key == pairs[k][0] * 256 + pairs[k][1] ? (uint32_t)k + 1u : e;
+    return e;
+}
+// Does any lane of the wave hold a listed pair?  One compare per pair straight into a lane mask, the rest is scalar: what every MCU pays.
+__device__ __forceinline__ bool color_exc_vote(int cb, int cr)
+{
+    const int pairs[JS_COLOR_EXC_PAIRS][2] = JS_COLOR_EXC_CBCR;
+    const int key = cb * 256 + cr;
+    uint64_t m = 0;
+    #pragma unroll
+    for (int k = 0; k < JS_COLOR_EXC_PAIRS; k++) m |= WBALLOT(key == pairs[k][0] * 256 + pairs[k][1]);
+    return m != 0ull;
+}
+// The index travels in the two lowest mantissa bits of Goff (an integer of at most nine bits: they are zero); whoever looks for it clears them.
+__device__ __forceinline__ float offs_tag(float goff, uint32_t e) { return __uint_as_float(__float_as_uint(goff) | e); }
+__device__ __forceinline__ void exc_table_fill(uint32_t* s_tab, uint32_t tid)
+{ if (tid < EXC_TAB_BYTES / 4u) s_tab[tid] = tid < 8u ? 0u : c_color_exc[(tid - 8u) >> 3][tid & 7u]; }
+// How much lower G is for a pixel of luminance cy (clamped) whose chroma sample carries tag e: 0.0f or 1.0f.  tab16: LDS address of the table + 16.
+__device__ __forceinline__ float exc_lookup(uint32_t tab16, uint32_t e, int cy)
+{
+    const uint32_t w = lds_r32(tab16 + e * 32u + (uint32_t)((cy >> 5) << 2));     // word (cy + 128) >> 5 of row e
+    return (float)__builtin_amdgcn_ubfe(w, (uint32_t)cy & 31u, 1u);              // bit (cy + 128) & 31
+}
+// fy: the clamped Y as a float, gsum: Y + Goff, less the exception
+__device__ __forceinline__ uint32_t offs_pixel(float fy, float gsum, float roff, float boff)
+{
+    uint32_t o = __builtin_amdgcn_cvt_pk_u8_f32(__fadd_rn(fy, boff), 0, 0u);
+    o = __builtin_amdgcn_cvt_pk_u8_f32(gsum, 1, o);
+    return __builtin_amdgcn_cvt_pk_u8_f32(__fadd_rn(fy, roff), 2, o);
+}
+
 // ---- IDCT term loop ------------------------------------------------------------------------------------------------------
 // What an instruction costs on gfx950 (tools/probes/pk_f32_rate.hip, profiles/r02_instr_rates.txt): plain fp32 / integer VOP2
 // with VGPR operands issue in 2.2 cycles per wave, anything with a DPP or SGPR operand, every conversion, min/max/med3, left
@@ -806,6 +870,53 @@ __device__ __forceinline__ void mcu_to_dib_fast(const JsImage& im, uint32_t img_
     }
 }
 
+// The same for 4:2:0 in the offset form (see chroma_offsets): the chroma phase of back_end_pairs has left the R, G, B offsets of the MCU's 64 chroma samples
+// at LDS address `co` (a plane of 64 floats per channel: three 8-byte reads fetch the lane's two samples).  Same lane-to-pixel mapping, same single 16-byte
+// DIB store per lane.  exc_any (wave-uniform): some sample of the MCU is one of the listed pairs -- its tag sits in the low bits of its Goff, and G of a pixel
+// is one lower where the pair's mask says so (exc_lookup); a pixel of any other sample reads row 0 of the table, zeros.  The int16 chroma blocks in the tile
+// are read for the plane stores only.
+__device__ __forceinline__ void mcu_to_dib_offs(const JsImage& im, uint32_t img_x, uint32_t img_y, const int16_t* tile, uint32_t plane_elems, uint32_t rs,
+                                                uint32_t lane, uint32_t ly0, uint32_t lq0, uint32_t my, uint32_t mx,
+                                                uint8_t* __restrict__ dibp, int16_t* __restrict__ planes, uint32_t pw, bool want_planes,
+                                                uint32_t co, uint32_t tab16, bool exc_any, uint64_t& bright, int& best_y, uint32_t& sum_y)
+{
+    constexpr uint32_t mw = 16, mh = 16;                         // 64 lanes x 4 pixels: one trip
+    const uint32_t y = ly0, x = lq0 * 4, py = my * mh + y, px = mx * mw + x;
+    uint8_t* mcu_low = dibp + ((size_t)(img_y - (my + 1u) * mh) * img_x + (size_t)mx * mw) * 4;
+    const uint2 qy = *reinterpret_cast<const uint2*>(tile + y * rs + x);
+    const uint32_t ci = (y / 2u) * 8u + x / 2u;                  // first chroma sample of the lane's four pixels (even)
+    const uint2 ur = lds_r64(co + ci * 4u), ug = lds_r64(co + 256u + ci * 4u), ub = lds_r64(co + 512u + ci * 4u);   // lanes of one row pair read the same 32 pairs: no conflict
+    const float ro[2] = { __uint_as_float(ur.x), __uint_as_float(ur.y) }, bo[2] = { __uint_as_float(ub.x), __uint_as_float(ub.y) };
+    const uint32_t gw[2] = { ug.x, ug.y };
+    bright4(qy, py * img_x + px, bright, best_y);
+    int ylo0, ylo1;                                              // s16_lo(w) >> 3 as ONE v_bfe_i32 (the compiler's own form is a shift pair)
+    asm("v_bfe_i32 %0, %1, 3, 13" : "=v"(ylo0) : "v"(qy.x)); asm("v_bfe_i32 %0, %1, 3, 13" : "=v"(ylo1) : "v"(qy.y));
+    const int cy[4] = { clamp_s8(ylo0), clamp_s8((int)qy.x >> 19), clamp_s8(ylo1), clamp_s8((int)qy.y >> 19) };
+    const float fy[4] = { (float)cy[0], (float)cy[1], (float)cy[2], (float)cy[3] };
+    float gs[4];                                                 // Y + Goff, both ways computed into the same registers: no copy where the paths join
+    if (exc_any) {
+        const uint32_t e[2] = { gw[0] & 3u, gw[1] & 3u };
+        #pragma unroll
+        for (int k = 0; k < 4; k++) gs[k] = __fadd_rn(__fsub_rn(fy[k], exc_lookup(tab16, e[k >> 1], cy[k])), __uint_as_float(gw[k >> 1] & ~3u));
+    } else {
+        #pragma unroll
+        for (int k = 0; k < 4; k++) gs[k] = __fadd_rn(fy[k], __uint_as_float(gw[k >> 1]));
+    }
+    uint4 v;
+    v.x = offs_pixel(fy[0], gs[0], ro[0], bo[0]); v.y = offs_pixel(fy[1], gs[1], ro[0], bo[0]);
+    v.z = offs_pixel(fy[2], gs[2], ro[1], bo[1]); v.w = offs_pixel(fy[3], gs[3], ro[1], bo[1]);
+    sum_y += (uint32_t)(cy[0] + cy[1] + cy[2] + cy[3] + 512);                              // nSumY += nFinalY (:4751)
+    *reinterpret_cast<uint4*>(mcu_low + ((mh - 1u - y) * img_x + x) * 4u) = v;
+    if (want_planes) {
+        const uint32_t wb = *reinterpret_cast<const uint32_t*>(tile + plane_elems + ci), wr = *reinterpret_cast<const uint32_t*>(tile + plane_elems + 64 + ci);
+        uint2 qcb, qcr;                                                                    // the four pixels' chroma samples (replicated form)
+        qcb.x = (wb & 0xFFFFu) * 0x10001u; qcb.y = (wb >> 16) * 0x10001u; qcr.x = (wr & 0xFFFFu) * 0x10001u; qcr.y = (wr >> 16) * 0x10001u;
+        int16_t* pb = planes + im.plane_off;
+        const size_t pi = (size_t)py * pw + px, psz = (size_t)pw * im.blk_ymax * 8;
+        *reinterpret_cast<uint2*>(pb + pi) = qy; *reinterpret_cast<uint2*>(pb + psz + pi) = qcb; *reinterpret_cast<uint2*>(pb + 2 * psz + pi) = qcr;
+    }
+}
+
 // One WAVE owns one MCU at a time: IDCT of its blocks in decode order (so self-overlapping replication,
 // SetFullRes :2498-2557, resolves exactly as in the reference: later blocks overwrite earlier ones),
 // samples staged in a wave-private LDS tile, then colour conversion and the MCU's DIB rows.  No
@@ -814,6 +925,7 @@ __device__ __forceinline__ void mcu_to_dib_fast(const JsImage& im, uint32_t img_
 struct BackEndCtx {
     const JsImage* im; const int16_t* cbase; const int16_t* dccum; uint8_t* dibp; int16_t* planes;
     WaveList L; const void* listmem; int16_t* tile; const uint32_t* s_meta; uint32_t lane, wg_in_img, wgs_in_img, wave;
+    uint32_t exc_tab;                                            // LDS address of the workgroup's exception table (the 4:2:0 kernel's offset form only)
 };
 // FAST: the layouts of mcu_to_dib_fast (EH, EV = chroma expansion); otherwise the general path.
 template <bool FAST, uint32_t EH, uint32_t EV>
@@ -945,6 +1057,10 @@ __device__ __forceinline__ void back_end_pairs(const BackEndCtx& C, uint64_t& br
     constexpr uint32_t quads = mw / 4, total = quads * mh;
     const uint32_t ly0 = lane / quads, lq0 = lane % quads;
     int best_y = -0x7FFFFFFF;
+    // OFFS: the offset form of the colour phase (chroma_offsets / mcu_to_dib_offs) -- 4:2:0 in its one-layout kernel.  The wave's offsets area lies
+    // behind its tile (the launch adds CO_BYTES to the per-wave size), the workgroup's exception table in C.exc_tab.
+    constexpr bool OFFS = HAND && EH == 2 && EV == 2;
+    const uint32_t co = lds_addr(tile) + plane_elems * 2u + 256u, co_w = co + (2u * l + hi) * 4u;   // co_w: where this lane's chroma sample (2l + hi, below) goes
     // per pair: does this half hold a block, where do the lane's two samples (2l, 2l+1: row l / 4, columns 2 (l % 4) and the next) go in the tile
     bool live[np]; uint32_t toff2[np], cmask[np];
     // DC-only mode: the reference does not run the IDCT at all (:1827); the DC difference (coefficient 0: low half of lane l == 0) is not part of the sum (:2381)
@@ -1005,6 +1121,7 @@ __device__ __forceinline__ void back_end_pairs(const BackEndCtx& C, uint64_t& br
         const uint32_t m_next = m + wstride < m_end ? m + wstride : m;   // (the last round fetches its own MCU again: no branch around the fetches)
         const uint32_t* p32n = reinterpret_cast<const uint32_t*>(C.cbase + (size_t)m_next * nb * 64);
         const int16_t* d16n = C.dccum + coef_off + (size_t)m_next * nb;
+        bool exc_any = false;
         #pragma unroll
         for (uint32_t p = 0; p < np; p++) {
             float acc0, acc1;
@@ -1018,9 +1135,21 @@ __device__ __forceinline__ void back_end_pairs(const BackEndCtx& C, uint64_t& br
             const uint32_t x0 = (uint32_t)((int)acc0 + dcl[p]), x1 = (uint32_t)((int)acc1 + dcl[p]);
             if (live[p]) *reinterpret_cast<uint32_t*>(tile + toff2[p]) = __builtin_amdgcn_perm(x1, x0, 0x05040100u);
             ld_dc(p, d16n);
+            if (OFFS && p == np - 1u) {
+                // Chroma phase, one sample per lane: half A holds Cb samples 2l and 2l + 1, half B the same of Cr.  v_permlane32_swap exchanges x0 of
+                // the upper half with x1 of the lower: x0 becomes Cb, x1 Cr, of sample 2l in lanes 0..31 and of sample 2l + 1 in lanes 32..63.
+                const auto sw = __builtin_amdgcn_permlane32_swap(x0, x1, false, false);
+                const int cb = clamp_s8(s16_lo(sw[0]) >> 3), cr = clamp_s8(s16_lo(sw[1]) >> 3);
+                const ChromaOff o = chroma_offsets(cb, cr);
+                exc_any = color_exc_vote(cb, cr);                 // wave-uniform: only then are the samples tagged and do the pixels look for their bit
+                float og = o.g;
+                if (exc_any) { asm volatile("; a listed pair in this MCU"); og = offs_tag(og, color_exc_index(cb, cr)); }   // (the asm keeps it a branch: as a select every MCU would pay for the tags)
+                lds_w32(co_w, __float_as_uint(o.r)); lds_w32(co_w + 256u, __float_as_uint(og)); lds_w32(co_w + 512u, __float_as_uint(o.b));
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        mcu_to_dib_fast<EH, EV>(im, img_x, img_y, tile, plane_elems, rs, quads, total, lane, ly0, lq0, my, mx, mw, mh, C.dibp, C.planes, pw, want_planes, bright, best_y, sum_y);
+        if (OFFS) mcu_to_dib_offs(im, img_x, img_y, tile, plane_elems, rs, lane, ly0, lq0, my, mx, C.dibp, C.planes, pw, want_planes, co, C.exc_tab + 16u, exc_any, bright, best_y, sum_y);
+        else mcu_to_dib_fast<EH, EV>(im, img_x, img_y, tile, plane_elems, rs, quads, total, lane, ly0, lq0, my, mx, mw, mh, C.dibp, C.planes, pw, want_planes, bright, best_y, sum_y);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     if (HAND) {
@@ -1051,6 +1180,7 @@ __global__ void __launch_bounds__(BK_THREADS, LAYOUT ? JS_BK_OCC : JS_BK_OCC - 2
     uint8_t* wave_mem = s_dyn + 64 * 64 * sizeof(float) + JS_MAX_BLK_PER_MCU * 4 + wave * (LIST_BYTES + tile_bytes);
     uint8_t* tail = s_dyn + 64 * 64 * sizeof(float) + JS_MAX_BLK_PER_MCU * 4 + BK_WAVES * (LIST_BYTES + tile_bytes);
     unsigned long long* s_bright = reinterpret_cast<unsigned long long*>(tail); uint32_t* s_sum = reinterpret_cast<uint32_t*>(tail + BK_WAVES * 8);
+    uint32_t* s_exc = reinterpret_cast<uint32_t*>(tail + BK_WAVES * 12);          // LAYOUT 1: the exception table of the offset form (EXC_TAB_BYTES)
     if ((uint32_t)(size_t)s_dyn != 0u) __builtin_trap();
 
     uint32_t lo = 0, hi = nimg;                                  // wg_base is an exclusive prefix, nimg+1 entries
@@ -1065,6 +1195,8 @@ __global__ void __launch_bounds__(BK_THREADS, LAYOUT ? JS_BK_OCC : JS_BK_OCC - 2
     C.im = &im; C.cbase = coef + im.coef_off * 64; C.dccum = dccum; C.dibp = dib + im.dib_off; C.planes = planes;
     C.L = wave_list(wave_mem, lane); C.listmem = wave_mem; C.tile = reinterpret_cast<int16_t*>(wave_mem + LIST_BYTES);
     C.s_meta = s_meta; C.lane = lane; C.wave = wave; C.wg_in_img = bx - wg_base[lo]; C.wgs_in_img = wg_base[lo + 1] - wg_base[lo];
+    C.exc_tab = lds_addr(s_exc);
+    if (LAYOUT == 1) exc_table_fill(s_exc, tid);
     __syncthreads();
 
     uint64_t bright = 0; uint32_t sum_y = 0;
@@ -1249,6 +1381,24 @@ __global__ void __launch_bounds__(256) k_color_sweep(uint32_t* __restrict__ out)
     const int y = ((int)(i >> 16) - 128) * 8, cb = ((int)((i >> 8) & 255u) - 128) * 8, cr = ((int)(i & 255u) - 128) * 8;
     const uint32_t a = ycc_to_bgra<true>(y, cb, cr, 1), b = ycc_to_bgra<false>(y, cb, cr, 1);
     out[i] = a == b ? a : 0xFF000000u | a;
+}
+// The same sweep through the offset form of the 4:2:0 colour phase: the offsets of the triple's chroma sample (chroma_offsets, tagged with its exception
+// pair), then the pixel as mcu_to_dib_offs forms it, the wave's vote and the table in LDS included.  Same output layout.
+__global__ void __launch_bounds__(256) k_color_offsets_sweep(uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t s_exc[EXC_TAB_BYTES / 4u];
+    exc_table_fill(s_exc, threadIdx.x);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const int cy = clamp_s8((((int)(i >> 16) - 128) * 8) >> 3), cb = clamp_s8((((int)((i >> 8) & 255u) - 128) * 8) >> 3), cr = clamp_s8((((int)(i & 255u) - 128) * 8) >> 3);
+    const ChromaOff o = chroma_offsets(cb, cr);
+    const bool exc_any = color_exc_vote(cb, cr);
+    const uint32_t gw = __float_as_uint(exc_any ? offs_tag(o.g, color_exc_index(cb, cr)) : o.g);
+    const float fy = (float)cy;
+    float gs;
+    if (exc_any) gs = __fadd_rn(__fsub_rn(fy, exc_lookup(lds_addr(s_exc) + 16u, gw & 3u, cy)), __uint_as_float(gw & ~3u));
+    else gs = __fadd_rn(fy, __uint_as_float(gw));
+    out[i] = offs_pixel(fy, gs, o.r, o.b);
 }
 
 // Position-keyed 64-bit checksum of every DIB: sum over 32-bit pixels of mix64(index<<32 | pixel).
@@ -1440,7 +1590,10 @@ int js_launch_idct_color(hipStream_t st, const JsImage* imgs, const uint32_t* wg
     if (!total_wgs) return 0;
     // tile_bytes: the largest per-wave tile any image of the launch needs (js_tile_bytes).  Ordinary images leave room for four
     // workgroups per CU; a 4 x 4 sampled image (32 x 32 MCU) needs more than the default 64 KiB limit and is opted in explicitly.
-    const size_t lds = 64 * 64 * sizeof(float) + JS_MAX_BLK_PER_MCU * 4 + (size_t)BK_WAVES * (LIST_BYTES + tile_bytes) + BK_WAVES * 12;
+    // The 4:2:0 kernel's offset form: CO_BYTES more per wave behind the tile and the exception table behind the workgroup's tail -- 39,328 bytes a workgroup,
+    // four of them still fit the CU's 160 KiB (profiles/r10_colour_offsets.txt).
+    if (layout == 1) tile_bytes += CO_BYTES;
+    const size_t lds = 64 * 64 * sizeof(float) + JS_MAX_BLK_PER_MCU * 4 + (size_t)BK_WAVES * (LIST_BYTES + tile_bytes) + BK_WAVES * 12 + (layout == 1 ? EXC_TAB_BYTES : 0u);
     if (lds > 160u * 1024u) return -2;
     if (lds > 64u * 1024u) {
         // The attribute belongs to the function object of the CURRENT device (one host thread per GPU is a supported use of the C ABI):
@@ -1490,6 +1643,8 @@ void js_launch_bright_probe(hipStream_t st, const JsImage* imgs, uint32_t img, c
 { hipLaunchKernelGGL(k_bright_probe, dim3(1), dim3(1), 0, st, imgs, img, side, planes, out8); }
 void js_launch_color_sweep(hipStream_t st, uint32_t* out)
 { hipLaunchKernelGGL(k_color_sweep, dim3(1u << 16), dim3(256), 0, st, out); }
+void js_launch_color_offsets_sweep(hipStream_t st, uint32_t* out)
+{ hipLaunchKernelGGL(k_color_offsets_sweep, dim3(1u << 16), dim3(256), 0, st, out); }
 void js_launch_color_stats(hipStream_t st, const JsImage* imgs, uint32_t img, const int16_t* planes, int hist_en, uint32_t* stats)
 { hipLaunchKernelGGL(k_color_stats, dim3(512), dim3(ST_THREADS), 0, st, imgs, img, planes, (uint32_t)(hist_en != 0), stats); }
 void js_launch_clip_order(hipStream_t st, const JsImage* imgs, uint32_t img, const int16_t* planes, uint32_t budget, uint32_t* out6)
