@@ -746,6 +746,86 @@ typedef int (*jsnoop_job_file_fn)(void* user, const JsnoopJobFile* f);      /* n
 int        jsnoop_job_run(JsnoopJob*, jsnoop_job_file_fn on_file, void* user, JsnoopJobStats* stats);
 int        jsnoop_job_file_result(const JsnoopJob*, int index, JsnoopJobFile* out);
 
+/* ---- carve: every embedded JPEG of a byte blob, found and walked on the device ------------------------------------------------------
+ * The other half of the reference's batch loop: "extract all" (-ext_all / bExtractAll of DoBatchFileProcess, source/JPEGsnoopCore.cpp:765-845;
+ * DoExtractEmbeddedJPEG :906-1091) takes any file -- a Motion-JPEG AVI, a RAW with previews, a JPEG with an EXIF thumbnail, a dump -- finds every
+ * FF D8 FF in it and walks the markers of each hit to its EOI; the search restarts one byte behind the previous START (:1063-1066), so nested
+ * thumbnails are frames of their own.  jsnoop_carve_run does that for a whole blob at once and leaves a table of frames; the frames go into a
+ * job through jsnoop_job_add_carved.  tests/carve_model.py is the definition; DESIGN.md section 4.14 has the contract and its reasons.
+ *
+ * The contract is structural: marker codes and segment lengths as CjfifDecode::DecodeMarker reads them in its strict mode, no segment's content.
+ * The blob is b[0..n), B(i) = b[i] for i < n and 0 past the end; n < 2^32.
+ *   terminator  i < n with b[i] = FF and B(i + 1) not 00 and not D0..D7 (what ends the skip over scan data).
+ *   candidate   p with b[p..p+3) = FF D8 FF and p + 3 <= n.  Every candidate gets a frame record; frames come in ascending start.
+ *   walk        from the candidate, marker by marker (fill bytes FF skipped): SOI goes on; EOI ends the frame (OK with a scan, NO_SOS without);
+ *               RST0-7 outside a scan, a code 00 / 02..BF, a byte that is not FF where a marker belongs and a length below 2 STOP it; C0..CF,
+ *               DA..FE and 01 are segments with a big-endian length; a segment or a fill run passing the end of the blob is NO_EOI; behind an SOS
+ *               segment the walk goes on at the next terminator (none: NO_EOI); more than max_markers markers is LIMIT.
+ * A frame: start; end (one past the EOI; n for NO_EOI; the detail position for STOPPED and LIMIT); status; for STOPPED the reason, for STOPPED and LIMIT
+ * the position and the byte found there (NOT_A_MARKER: the byte; RST_OUTSIDE_SCAN, UNKNOWN_MARKER and LIMIT: the marker code, at its own position;
+ * BAD_LENGTH: the length, at the length field); seen (JSNOOP_CARVE_SEEN_*); of the first SOFn (C0-C3, C5-C7, C9-CB, CD-CF) its code, precision, height,
+ * width and component count (0 without one); sos_pos (the FF of the first SOS), scan_start (behind its segment), scans, markers; parent: the
+ * innermost earlier frame with status OK whose [start, end) holds this frame's start, or -1 -- what tells a thumbnail from the next video frame.
+ *
+ * jsnoop_carve_run: where = 0, blob is host memory and goes to the device through page-locked staging; where = 1, blob is memory of the carve's
+ * device, read in place (any alignment).  Two waits: the totals of terminators and candidates come back and size the lists, then the records
+ * come back.  Lists and records (4 bytes per terminator, 68 per candidate), the tile counts and for where = 0 the blob's copy are the scratch;
+ * above max_scratch_bytes (0 = half of the device's free memory) the call is refused with a text before any of it is allocated beyond the counts.
+ * -1 + jsnoop_last_error(): a NULL carve, spec or (with len > 0) blob, len >= 2^32, a bad struct_size (read like JsnoopTuning's), a where
+ * other than 0 / 1, scratch over budget, a device error.  A refused call leaves the last table as it was.  max_markers = 0 means 4096.
+ * A fill run is walked byte by byte: a blob of FF D8 followed by megabytes of FF costs one lane that many steps.
+ * jsnoop_carve_host: the same table on the host alone, no device needed: the number of frames (frames[0 .. min(count, cap)) written), or -1.  */
+typedef struct JsnoopCarve JsnoopCarve;
+#define JSNOOP_CARVE_OK       0
+#define JSNOOP_CARVE_NO_SOS   1
+#define JSNOOP_CARVE_NO_EOI   2
+#define JSNOOP_CARVE_STOPPED  3
+#define JSNOOP_CARVE_LIMIT    4
+#define JSNOOP_CARVE_NOT_A_MARKER      1
+#define JSNOOP_CARVE_RST_OUTSIDE_SCAN  2
+#define JSNOOP_CARVE_BAD_LENGTH        3
+#define JSNOOP_CARVE_UNKNOWN_MARKER    4
+#define JSNOOP_CARVE_SEEN_SOI_AGAIN 1u
+#define JSNOOP_CARVE_SEEN_DQT       2u
+#define JSNOOP_CARVE_SEEN_DHT       4u
+#define JSNOOP_CARVE_SEEN_DRI       8u
+#define JSNOOP_CARVE_SEEN_AVI1      16u
+/* units of work of the carve kernels (jsnoop_carve.hip), for tests that slide patterns across their seams */
+#define JSNOOP_CARVE_LANE   16u        /* bytes a lane classifies at a time, one 16-byte load */
+#define JSNOOP_CARVE_WAVE   1024u      /* ... and a wave: 64 lanes */
+#define JSNOOP_CARVE_TILE   16384u     /* bytes of a workgroup's tile: 4 waves, 4 loads a lane; tiles start at multiples of it counted from the 16-byte boundary at or below the blob */
+#define JSNOOP_CARVE_WALK   256u       /* candidates of one workgroup of the walk kernel, one a lane */
+#define JSNOOP_CARVE_REC_WORDS 16u     /* words of a record in device memory (jsnoop_carve_frames_dev): start, end, status | reason << 8 | byte << 16 | seen << 24,
+                                          detail position, sof_code | precision << 8 | components << 16, width | height << 16, sos_pos, scan_start, scans, markers, 6 x 0 */
+typedef struct JsnoopCarveSpec { uint32_t struct_size; uint32_t max_markers; uint64_t max_scratch_bytes; } JsnoopCarveSpec;
+typedef struct JsnoopCarveFrame {
+    uint32_t struct_size;           /* jsnoop_carve_frame: set to sizeof(your JsnoopCarveFrame) (or 0: this header's); no byte past it is written */
+    uint32_t start, end;
+    int32_t  status, reason;        /* JSNOOP_CARVE_*; reason 0 unless STOPPED */
+    uint32_t detail_pos, detail_byte;
+    uint32_t seen;
+    uint32_t sof_code, precision, width, height, components;
+    uint32_t sos_pos, scan_start, scans, markers;
+    int32_t  parent;
+} JsnoopCarveFrame;
+JsnoopCarve* jsnoop_carve_create(int device);                                   /* NULL + jsnoop_last_error() without that device */
+void         jsnoop_carve_destroy(JsnoopCarve*);
+void         jsnoop_carve_spec_defaults(JsnoopCarveSpec* out);                  /* max_markers 4096, max_scratch_bytes 0; NULL tolerated */
+int          jsnoop_carve_run(JsnoopCarve*, const JsnoopCarveSpec*, const void* blob, uint64_t len, int where);
+int64_t      jsnoop_carve_host(const JsnoopCarveSpec*, const void* blob, uint64_t len, JsnoopCarveFrame* frames, uint64_t cap);
+int64_t      jsnoop_carve_count(const JsnoopCarve*);                            /* frames of the last run */
+int          jsnoop_carve_frame(const JsnoopCarve*, int64_t k, JsnoopCarveFrame* out);
+int64_t      jsnoop_carve_frames(const JsnoopCarve*, JsnoopCarveFrame* out, uint64_t cap);   /* this header's struct, struct_size set; returns how many were written */
+const void*  jsnoop_carve_frames_dev(const JsnoopCarve*);                       /* count x JSNOOP_CARVE_REC_WORDS words in device memory (no parent); valid until the next run / destroy */
+int          jsnoop_carve_lists_dev(const JsnoopCarve*, const uint32_t** terminators, const uint32_t** candidates);   /* the two ascending position lists, device memory */
+int          jsnoop_carve_totals(const JsnoopCarve*, uint64_t* terminators, uint64_t* candidates);
+/* what = 0 the records, 1 the terminator list, 2 the candidate list: copied device-to-device into caller memory of the carve's device and waited for.
+ * Returns the bytes copied (0 for an empty one); -1: a NULL carve or destination, an unknown `what`, cap below the size, a device error.             */
+int64_t      jsnoop_carve_copy(JsnoopCarve*, int what, void* dev_dst, uint64_t cap);
+/* Adds blob[start, end) of every frame with status OK (and NO_EOI if include_no_eoi) to the job, each with the copy jsnoop_job_add_file makes, in table order.
+ * Returns how many it added, *first_index (may be NULL) = the file index of the first (-1: none); -1 on a bad argument or a frame outside the blob, nothing added. */
+int          jsnoop_job_add_carved(JsnoopJob*, const uint8_t* blob, uint64_t len, const JsnoopCarveFrame* frames, int64_t nframes, int include_no_eoi, int* first_index);
+
 #ifdef __cplusplus
 }
 #endif

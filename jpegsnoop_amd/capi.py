@@ -139,6 +139,29 @@ class ExportSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("jfif", C.c_int32)]
 
 
+CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
+CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
+CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
+CARVE_LANE = 16         # JSNOOP_CARVE_LANE of include/jsnoop_gpu.h: bytes a lane classifies at a time, one 16-byte load
+CARVE_WAVE = 1024       # JSNOOP_CARVE_WAVE: ... and a wave
+CARVE_TILE = 16384      # JSNOOP_CARVE_TILE: bytes of a workgroup's tile, counted from the 16-byte boundary at or below the blob
+CARVE_WALK = 256        # JSNOOP_CARVE_WALK: candidates of one workgroup of the walk kernel
+CARVE_REC_WORDS = 16    # JSNOOP_CARVE_REC_WORDS: words of a record in device memory
+
+
+class CarveSpec(C.Structure):
+    """JsnoopCarveSpec of include/jsnoop_gpu.h: the marker cap of one walk and the scratch budget of one call (0 = half of the device's free memory)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_markers", C.c_uint32), ("max_scratch_bytes", C.c_uint64)]
+
+
+class CarveFrame(C.Structure):
+    """JsnoopCarveFrame of include/jsnoop_gpu.h: one candidate of a carved blob and how its marker walk ended."""
+    _fields_ = [("struct_size", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32),
+                ("detail_pos", C.c_uint32), ("detail_byte", C.c_uint32), ("seen", C.c_uint32), ("sof_code", C.c_uint32), ("precision", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_uint32), ("sos_pos", C.c_uint32), ("scan_start", C.c_uint32),
+                ("scans", C.c_uint32), ("markers", C.c_uint32), ("parent", C.c_int32)]
+
+
 JOB_FILE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(JobFile))
 
 XC_BACKEND_GENERIC, XC_WRITE_V1, XC_NO_TAIL, XC_SIDE_EXACT, XC_CAND_VERIFY, XC_UNSTUFF_3PASS, XC_DC_GENERIC = 1, 2, 4, 8, 16, 32, 64
@@ -299,6 +322,19 @@ SIGNATURES = {
     "jsnoop_job_clear": (None, [_p]),
     "jsnoop_job_run": (_i, [_p, JOB_FILE_FN, _p, C.POINTER(JobStats)]),
     "jsnoop_job_file_result": (_i, [_p, _i, C.POINTER(JobFile)]),
+    "jsnoop_carve_create": (_p, [_i]),
+    "jsnoop_carve_destroy": (None, [_p]),
+    "jsnoop_carve_spec_defaults": (None, [C.POINTER(CarveSpec)]),
+    "jsnoop_carve_run": (_i, [_p, C.POINTER(CarveSpec), _p, C.c_uint64, _i]),
+    "jsnoop_carve_host": (C.c_int64, [C.POINTER(CarveSpec), _p, C.c_uint64, C.POINTER(CarveFrame), C.c_uint64]),
+    "jsnoop_carve_count": (C.c_int64, [_p]),
+    "jsnoop_carve_frame": (_i, [_p, C.c_int64, C.POINTER(CarveFrame)]),
+    "jsnoop_carve_frames": (C.c_int64, [_p, C.POINTER(CarveFrame), C.c_uint64]),
+    "jsnoop_carve_frames_dev": (_p, [_p]),
+    "jsnoop_carve_lists_dev": (_i, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "jsnoop_carve_totals": (_i, [_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jsnoop_carve_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_job_add_carved": (_i, [_p, _p, C.c_uint64, C.POINTER(CarveFrame), C.c_int64, _i, _PI]),
 }
 
 _lib = None

@@ -344,14 +344,45 @@ public:
     const BatchFileInfo* GetBatchFileEntry(unsigned nFileInd) const { return nFileInd < m_batchFiles.size() ? &m_batchFiles[nFileInd] : nullptr; }
 
     void     JobSetOptions(const JsnoopJobOptions& o) { m_jobOpt = o; m_bJobOpt = true; }
+    // "Extract all" for one blob (DoExtractEmbeddedJPEG, source/JPEGsnoopCore.cpp:906-1091, for every hit at once): the frame table of every FF D8 FF in
+    // [pBlob, pBlob + nLen), found and walked on `nDevice` (jsnoop_carve_* of include/jsnoop_gpu.h).  false + jsnoop_last_error() on a refusal.
+    static bool CarveBlob(const uint8_t* pBlob, size_t nLen, std::vector<JsnoopCarveFrame>& frames, int nDevice = 0, const JsnoopCarveSpec* pSpec = nullptr)
+    {
+        frames.clear();
+        JsnoopCarve* c = jsnoop_carve_create(nDevice);
+        if (!c) return false;
+        JsnoopCarveSpec spec; jsnoop_carve_spec_defaults(&spec);
+        bool ok = jsnoop_carve_run(c, pSpec ? pSpec : &spec, pBlob, nLen, 0) == 0;
+        if (ok) { frames.resize((size_t)jsnoop_carve_count(c)); ok = jsnoop_carve_frames(c, frames.data(), frames.size()) == (int64_t)frames.size(); }
+        jsnoop_carve_destroy(c);
+        return ok;
+    }
+    // With bExtractAll the job's files are the carved frames of the listed files: which listed file a job index came from, its frame number there (from 1, the
+    // number in the reference's name.000001.jpg) and the frame's record.
+    struct CarvedInfo { unsigned nFileInd; unsigned nFrame; JsnoopCarveFrame frame; };
+    const CarvedInfo* GetCarvedEntry(unsigned nJobInd) const { return nJobInd < m_carved.size() ? &m_carved[nJobInd] : nullptr; }
     // Runs the listed files as one job over `devices` (empty: one shard per visible device); fn sees every file once, on this thread -- f.batch / f.image
     // take the per-image jsnoop_batch_* calls while it runs.  A false return cancels.  Returns jsnoop_job_run's value (0 done, 1 cancelled, -1 error).
-    int      JobRun(const std::function<bool(const JsnoopJobFile&)>& fn, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr)
+    // With bExtractAll every listed file is carved (on the first device of the list) and its frames with status OK are the job's files, in place of the file:
+    // f.index then counts carved frames, GetCarvedEntry(f.index) says where each came from.  A listed file that cannot be read yields no frame.
+    int      JobRun(const std::function<bool(const JsnoopJobFile&)>& fn, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr, bool bExtractAll = false)
     {
         JsnoopJob* j = jsnoop_job_create(devices.empty() ? nullptr : devices.data(), (int)devices.size());
         if (!j) return -1;
         int rc = (m_bJobOpt && jsnoop_job_set_options(j, &m_jobOpt)) ? -1 : 0;
-        for (size_t i = 0; rc == 0 && i < m_batchFiles.size(); i++) if (jsnoop_job_add_path(j, m_batchFiles[i].strSrc.c_str()) < 0) rc = -1;
+        m_carved.clear();
+        for (size_t i = 0; rc == 0 && i < m_batchFiles.size(); i++) {
+            if (!bExtractAll) { if (jsnoop_job_add_path(j, m_batchFiles[i].strSrc.c_str()) < 0) rc = -1; continue; }
+            std::vector<uint8_t> blob; std::vector<JsnoopCarveFrame> frames;
+            if (FILE* fp = fopen(m_batchFiles[i].strSrc.c_str(), "rb")) {
+                uint8_t tmp[65536]; size_t n;
+                while ((n = fread(tmp, 1, sizeof tmp, fp)) > 0) blob.insert(blob.end(), tmp, tmp + n);
+                fclose(fp);
+            }
+            if (!CarveBlob(blob.data(), blob.size(), frames, devices.empty() ? 0 : devices[0])) { rc = -1; break; }
+            if (jsnoop_job_add_carved(j, blob.data(), blob.size(), frames.data(), (int64_t)frames.size(), 0, nullptr) < 0) { rc = -1; break; }
+            for (size_t k = 0; k < frames.size(); k++) if (frames[k].status == JSNOOP_CARVE_OK) m_carved.push_back({ (unsigned)i, (unsigned)k + 1u, frames[k] });
+        }
         if (rc == 0) {
             auto thunk = [](void* u, const JsnoopJobFile* f) -> int { return (*static_cast<const std::function<bool(const JsnoopJobFile&)>*>(u))(*f) ? 0 : 1; };
             rc = jsnoop_job_run(j, fn ? static_cast<jsnoop_job_file_fn>(thunk) : nullptr, const_cast<void*>(static_cast<const void*>(&fn)), pStats);
@@ -362,7 +393,9 @@ public:
     // DoBatchFileProcess for every listed file at once.  With bWriteLog each file gets <dirDst>/<relative path>.txt, the name GenBatchFileListSingle derives
     // (:649-650), holding what BatchLogSave writes: the DecodeScanImg report.  A progressive file has no such report (the reference refuses SOF2): the
     // library's own wording of that goes in its place; a refused or unreadable file gets its message.  Returns the number of files decoded, or -1.
-    int      DoBatchFileProcessAll(bool bWriteLog, const std::string& dirDst, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr)
+    // bExtractAll (the reference's parameter of the same name, :765): every listed file is carved and its frames are decoded in place of the file; the report
+    // of frame k of a file goes to <dirDst>/<relative path>.<k, six digits>.txt beside the name the reference gives the extracted frame (:1052-1056).
+    int      DoBatchFileProcessAll(bool bWriteLog, const std::string& dirDst, const std::vector<int>& devices = {}, JsnoopJobStats* pStats = nullptr, bool bExtractAll = false)
     {
         namespace fs = std::filesystem;
         JsnoopJobOptions o; if (m_bJobOpt) o = m_jobOpt; else jsnoop_job_options_defaults(&o);
@@ -372,8 +405,10 @@ public:
         int nOk = 0;
         const int rc = JobRun([&](const JsnoopJobFile& f) {
             if (f.status == JSNOOP_JOB_OK) nOk++;
-            if (!bWriteLog || f.index < 0 || (size_t)f.index >= m_batchFiles.size()) return true;
-            const fs::path log = fs::path(dirDst) / (m_batchFiles[(size_t)f.index].strRel + ".txt");
+            if (!bWriteLog || f.index < 0 || (size_t)f.index >= (bExtractAll ? m_carved.size() : m_batchFiles.size())) return true;
+            std::string strName = bExtractAll ? m_batchFiles[m_carved[(size_t)f.index].nFileInd].strRel : m_batchFiles[(size_t)f.index].strRel;
+            if (bExtractAll) { char num[16]; snprintf(num, sizeof num, ".%06u", m_carved[(size_t)f.index].nFrame); strName += num; }
+            const fs::path log = fs::path(dirDst) / (strName + ".txt");
             std::error_code ec; fs::create_directories(log.parent_path(), ec);
             FILE* fp = fopen(log.string().c_str(), "w");
             if (!fp) return true;
@@ -382,7 +417,7 @@ public:
             else if (jsnoop_batch_log(f.batch, f.image, 0, 0, 0, thunk, fp)) fprintf(fp, "W:%s\n", jsnoop_last_error());
             fclose(fp);
             return true;
-        }, devices, pStats);
+        }, devices, pStats, bExtractAll);
         m_jobOpt = saved; m_bJobOpt = bSaved;
         return rc < 0 ? -1 : nOk;
     }
@@ -392,4 +427,5 @@ private:
     CwindowBufView m_view; std::vector<uint8_t> m_file; std::string m_strPathName; bool m_bFileAnalyzed = false;
     CimgDecodeGpu* m_pImgDec; JsnoopBatch* m_b = nullptr;
     std::vector<BatchFileInfo> m_batchFiles; std::string m_strBatchDirSrc; JsnoopJobOptions m_jobOpt{}; bool m_bJobOpt = false;
+    std::vector<CarvedInfo> m_carved;
 };

@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 #include "jsnoop_host.h"
+#include "jsnoop_carve_check.h"
 
 namespace {
 
@@ -280,6 +281,15 @@ int jsnoop_job_add_file(JsnoopJob* j, const uint8_t* file, size_t len)
     JobEntry& e = j->files.back(); if (len) e.bytes.assign(file, file + len);
     reset_result(e, (int)j->files.size() - 1);
     return (int)j->files.size() - 1;
+}
+int jsnoop_job_add_carved(JsnoopJob* j, const uint8_t* blob, uint64_t len, const JsnoopCarveFrame* frames, int64_t nframes, int include_no_eoi, int* first_index)
+{
+    if (!j || (!blob && len)) { js_set_error("jsnoop_job_add_carved: null argument"); return -1; }
+    std::vector<int64_t> pick;
+    if (js_carve_pick(frames, nframes, len, include_no_eoi, &pick)) return -1;
+    if (first_index) *first_index = pick.empty() ? -1 : (int)j->files.size();
+    for (int64_t k : pick) if (jsnoop_job_add_file(j, blob + frames[k].start, (size_t)(frames[k].end - frames[k].start)) < 0) return -1;
+    return (int)pick.size();
 }
 int jsnoop_job_add_path(JsnoopJob* j, const char* path)
 {

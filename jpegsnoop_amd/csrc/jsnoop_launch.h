@@ -122,3 +122,10 @@ int  js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t
 int  js_launch_export_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
                             uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
                             uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
+// jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
+// head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
+// the two totals as 64-bit words).  0, -1 on a launch error.
+int  js_launch_carve_count(hipStream_t st, const uint8_t* base, uint32_t head, uint64_t n, uint32_t tiles, uint32_t* counts);
+// ... second phase: k_carve_emit writes the two ascending position lists, k_carve_walk one 64-byte record per candidate.
+int  js_launch_carve_walk(hipStream_t st, const uint8_t* base, uint32_t head, uint64_t n, uint32_t tiles, const uint32_t* counts, uint32_t nterm, uint32_t ncand,
+                          uint32_t max_markers, uint32_t* term, uint32_t* cand, uint32_t* recs);

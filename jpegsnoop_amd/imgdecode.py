@@ -1102,6 +1102,15 @@ class JpegJob:
         buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
         return self._chk(self._lib.jsnoop_job_add_file(self._h, C.cast(buf, C.c_void_p), len(data)), "job_add_file")
 
+    def add_carved(self, data, frames, include_no_eoi=False) -> list:
+        """Adds data[start:end] of every frame of a carve's table (Carve.frames / carve_host) with status OK -- and NO_EOI if asked -- as a file of its own
+        (jsnoop_job_add_carved).  `data` is host bytes or a uint8 numpy array.  Returns the file indices, in table order."""
+        buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        first = C.c_int(-1)
+        n = self._chk(self._lib.jsnoop_job_add_carved(self._h, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, _carve_table(frames), len(frames),
+                                                      int(bool(include_no_eoi)), C.byref(first)), "job_add_carved")
+        return list(builtins.range(first.value, first.value + n))
+
     def add_path(self, path) -> int:
         """Adds a file by path: read by the shard that owns it, in the round that decodes it."""
         import os
@@ -1151,6 +1160,124 @@ class JpegJob:
             self.close()
         except Exception:
             pass
+
+
+CARVE_FIELDS = tuple(name for name, _ in capi.CarveFrame._fields_[1:])
+
+
+def _carve_spec(lib, max_markers, max_scratch_bytes) -> "capi.CarveSpec":
+    s = capi.CarveSpec()
+    lib.jsnoop_carve_spec_defaults(C.byref(s))
+    if max_markers is not None:
+        s.max_markers = int(max_markers)
+    s.max_scratch_bytes = int(max_scratch_bytes)
+    return s
+
+
+def _carve_dicts(arr, n) -> list:
+    return [{k: getattr(arr[i], k) for k in CARVE_FIELDS} for i in builtins.range(n)]
+
+
+def _carve_table(frames):
+    """A list of frame dicts (Carve.frames / carve_host) as a JsnoopCarveFrame array."""
+    arr = (capi.CarveFrame * max(1, len(frames)))()
+    for a, f in zip(arr, frames):
+        a.struct_size = C.sizeof(capi.CarveFrame)
+        for k in CARVE_FIELDS:
+            setattr(a, k, f[k])
+    return arr
+
+
+def carve_host(data, max_markers=None) -> list:
+    """The frame table of `data` (bytes or a uint8 numpy array) computed on the host alone (jsnoop_carve_host): no device needed."""
+    lib = capi.load(require_device=False)
+    buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+    spec = _carve_spec(lib, max_markers, 0)
+    ptr = buf.ctypes.data_as(C.c_void_p) if buf.size else None
+    n = lib.jsnoop_carve_host(C.byref(spec), ptr, buf.size, None, 0)
+    if n < 0:
+        raise RuntimeError("carve_host failed: " + capi.last_error())
+    arr = (capi.CarveFrame * max(1, n))()
+    if lib.jsnoop_carve_host(C.byref(spec), ptr, buf.size, arr, n) != n:
+        raise RuntimeError("carve_host failed: " + capi.last_error())
+    return _carve_dicts(arr, n)
+
+
+class Carve:
+    """Every embedded JPEG of a byte blob, found and walked on the device: jsnoop_carve_* of include/jsnoop_gpu.h, the reference's "extract all"
+    (DoExtractEmbeddedJPEG, source/JPEGsnoopCore.cpp:906-1091) for a whole blob at once.  run() takes bytes or a numpy array (uploaded through the
+    library's page-locked staging) or a uint8 torch tensor on the carve's device (read in place, any alignment)."""
+
+    def __init__(self, device=0, max_markers=None, max_scratch_bytes=0):
+        self._lib = capi.load()
+        self._h = self._lib.jsnoop_carve_create(int(device))
+        if not self._h:
+            raise RuntimeError("jsnoop_carve_create failed: " + capi.last_error())
+        self.device = int(device)
+        self._spec = _carve_spec(self._lib, max_markers, max_scratch_bytes)
+
+    def close(self):
+        if self._h:
+            self._lib.jsnoop_carve_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_spec(self, max_markers=None, max_scratch_bytes=0):
+        """The marker cap of a walk (None: the library's 4096) and the scratch budget (0: half of the device's free memory) of the runs that follow."""
+        self._spec = _carve_spec(self._lib, max_markers, max_scratch_bytes)
+
+    def run(self, data) -> int:
+        """Carves `data`; returns the number of frames (one per FF D8 FF).  A refused call (scratch over budget, ...) raises and leaves the last table."""
+        if isinstance(data, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+            rc = self._lib.jsnoop_carve_run(self._h, C.byref(self._spec), buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, 0)
+        else:
+            import torch
+            if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.is_cuda and data.device.index == self.device and data.is_contiguous()):
+                raise TypeError("Carve.run takes bytes, a numpy array or a contiguous uint8 torch tensor on device %d" % self.device)
+            torch.cuda.current_stream(data.device).synchronize()      # the carve runs on its own stream: the tensor's bytes must be there
+            rc = self._lib.jsnoop_carve_run(self._h, C.byref(self._spec), data.data_ptr() if data.numel() else None, data.numel(), 1)
+        if rc < 0:
+            raise RuntimeError("carve_run failed: " + capi.last_error())
+        return len(self)
+
+    def __len__(self): return int(self._lib.jsnoop_carve_count(self._h))
+
+    def totals(self):
+        """(terminators, candidates) of the last run."""
+        t, c = C.c_uint64(), C.c_uint64()
+        self._lib.jsnoop_carve_totals(self._h, C.byref(t), C.byref(c))
+        return t.value, c.value
+
+    def frames(self) -> list:
+        """The frame table of the last run: one dict per candidate, ascending start (fields: JsnoopCarveFrame's)."""
+        n = len(self)
+        arr = (capi.CarveFrame * max(1, n))()
+        if self._lib.jsnoop_carve_frames(self._h, arr, n) != n:
+            raise RuntimeError("carve_frames failed: " + capi.last_error())
+        return _carve_dicts(arr, n)
+
+    def _dev_words(self, what, words):
+        import torch
+        out = torch.empty(words, dtype=torch.int32, device=torch.device("cuda", self.device))
+        if self._lib.jsnoop_carve_copy(self._h, what, out.data_ptr() if words else None, words * 4) != words * 4:
+            raise RuntimeError("carve_copy failed: " + capi.last_error())
+        return out
+
+    def frames_to_torch(self):
+        """The records as they lie in device memory: an int32 tensor [frames, CARVE_REC_WORDS] (a copy; words are unsigned, see include/jsnoop_gpu.h)."""
+        n = len(self)
+        return self._dev_words(0, n * capi.CARVE_REC_WORDS).view(n, capi.CARVE_REC_WORDS)
+
+    def lists_to_torch(self):
+        """(terminators, candidates): the two ascending position lists of the last run, int32 tensors holding unsigned positions (copies)."""
+        nt, nc = self.totals()
+        return self._dev_words(1, nt), self._dev_words(2, nc)
 
 
 def dib_checksum_numpy(dib: np.ndarray) -> int:
