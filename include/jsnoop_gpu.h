@@ -645,6 +645,26 @@ int          jsnoop_batch_export_file(const JsnoopBatch*, int k, const void** de
 int64_t      jsnoop_batch_read_export(JsnoopBatch*, int k, void* host_dst, uint64_t cap);
 int64_t      jsnoop_batch_export_copy(JsnoopBatch*, int k, void* dev_dst, uint64_t cap);
 int          jsnoop_export_jpeg(JsnoopDecoder*, const char* path);
+/* Huffman tables of the export.  jsnoop_batch_export_jpeg_coded is jsnoop_batch_export_jpeg with a second spec: huffman = JSNOOP_HUFFMAN_ANNEX_K
+ * gives the same bytes; JSNOOP_HUFFMAN_OPTIMAL counts the Annex F symbols of every listed entry and builds its own tables on the device
+ * (T.81 Annex K.2 per table: the reserved 257th symbol, on equal counts the largest symbol first, Adjust_BITS, symbols in the order of
+ * (code size before the adjustment, symbol value)) and writes them in place of the Annex K ones: DHT DC0, AC0 (DC1, AC1), one segment
+ * each, Lh = 19 + symbols.  Everything else of the file, the result words, `detail`, the two waits and the accessors above are unchanged;
+ * tests/export_opt_model.py is the definition, byte for byte, DESIGN.md section 4.15 the contract.  In this mode alone an image of 2^26
+ * blocks or more is JSNOOP_EXPORT_UNSUPPORTED (32-bit symbol counters).  struct_size is read like JsnoopExportSpec's; a huffman value
+ * other than the two is refused.
+ * jsnoop_batch_export_tables: entry k of the last export and slot 0..3 (2 x table id + class; a grey image has 0 and 1): the symbol counts
+ * (freq[256], zero where the symbol did not occur) and the table that was written (counts per length 1..16, symbols in code order, *nsym
+ * of them; the rest of symbols[256] zero), by one staged copy from the device on demand; any output pointer may be NULL.  -1 with a text
+ * for an entry that is not OK, a slot the image does not have, and a last export with huffman = JSNOOP_HUFFMAN_ANNEX_K.
+ * jsnoop_export_jpeg_coded: jsnoop_export_jpeg with a coding spec (NULL: the defaults).                                                  */
+#define JSNOOP_HUFFMAN_ANNEX_K 0
+#define JSNOOP_HUFFMAN_OPTIMAL 1
+typedef struct JsnoopExportCoding { uint32_t struct_size; int32_t huffman; } JsnoopExportCoding;
+void         jsnoop_export_coding_defaults(JsnoopExportCoding* out);                           /* huffman 0; NULL tolerated */
+int          jsnoop_batch_export_jpeg_coded(JsnoopBatch*, const JsnoopExportSpec*, const JsnoopExportCoding*, const int* images, int n);
+int          jsnoop_batch_export_tables(JsnoopBatch*, int k, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256]);
+int          jsnoop_export_jpeg_coded(JsnoopDecoder*, const char* path, const JsnoopExportCoding*);
 
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and

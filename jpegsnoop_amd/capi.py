@@ -139,6 +139,25 @@ class ExportSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("jfif", C.c_int32)]
 
 
+HUFFMAN_ANNEX_K, HUFFMAN_OPTIMAL = 0, 1
+HUFFMAN_MODES = {"annex_k": HUFFMAN_ANNEX_K, "optimal": HUFFMAN_OPTIMAL}
+
+
+class ExportCoding(C.Structure):
+    """JsnoopExportCoding of include/jsnoop_gpu.h: which Huffman tables jsnoop_batch_export_jpeg_coded writes (Annex K's, or each image's own, built on the device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("huffman", C.c_int32)]
+
+
+def export_coding(lib, huffman):
+    """The JsnoopExportCoding of huffman = "annex_k" | "optimal"."""
+    if huffman not in HUFFMAN_MODES:
+        raise ValueError('huffman must be "annex_k" or "optimal", not %r' % (huffman,))
+    c = ExportCoding()
+    lib.jsnoop_export_coding_defaults(C.byref(c))
+    c.huffman = HUFFMAN_MODES[huffman]
+    return c
+
+
 CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
 CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
 CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
@@ -310,6 +329,10 @@ SIGNATURES = {
     "jsnoop_batch_read_export": (C.c_int64, [_p, _i, _p, C.c_uint64]),
     "jsnoop_batch_export_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
     "jsnoop_export_jpeg": (_i, [_p, C.c_char_p]),
+    "jsnoop_export_coding_defaults": (None, [C.POINTER(ExportCoding)]),
+    "jsnoop_batch_export_jpeg_coded": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), _PI, _i]),
+    "jsnoop_batch_export_tables": (_i, [_p, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "jsnoop_export_jpeg_coded": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

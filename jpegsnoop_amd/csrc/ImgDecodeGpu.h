@@ -269,9 +269,15 @@ public:
     { return files.size() == dst.size() && jsnoop_batch_pack_planes(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
     // the listed files (empty list: all) written back as baseline JPEG files, entropy-coded on the device into memory the batch owns (jsnoop_batch_export_jpeg: waits twice;
     // valid until the next export, clear, upload or destroy); entry k through BatchExportFile / BatchReadExport (false where the image could not be exported: nResult says why)
-    bool     BatchExportJpeg(const std::vector<int>& files = {}, bool bJfif = true)
+    // bOptimal: every file with its own Huffman tables, built on the device (jsnoop_batch_export_jpeg_coded, JSNOOP_HUFFMAN_OPTIMAL); BatchExportTables reads them back
+    bool     BatchExportJpeg(const std::vector<int>& files = {}, bool bJfif = true, bool bOptimal = false)
     { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;
-      return jsnoop_batch_export_jpeg(m_b, &spec, files.empty() ? nullptr : files.data(), files.empty() ? jsnoop_batch_count(m_b) : (int)files.size()) == 0; }
+      const int* p = files.empty() ? nullptr : files.data(); const int n = files.empty() ? jsnoop_batch_count(m_b) : (int)files.size();
+      if (!bOptimal) return jsnoop_batch_export_jpeg(m_b, &spec, p, n) == 0;
+      JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = JSNOOP_HUFFMAN_OPTIMAL;
+      return jsnoop_batch_export_jpeg_coded(m_b, &spec, &coding, p, n) == 0; }
+    bool     BatchExportTables(int k, int nSlot, uint8_t anCounts[16], uint8_t anSymbols[256], uint32_t& nSymbols, uint32_t anFreq[256])
+    { return jsnoop_batch_export_tables(m_b, k, nSlot, anCounts, anSymbols, &nSymbols, anFreq) == 0; }
     int      BatchExportCount() const { return jsnoop_batch_export_count(m_b); }
     bool     BatchExportFile(int k, const void*& pDev, uint64_t& nLen, int& nResult, uint32_t& nDetail, int& nFileInd) const { return jsnoop_batch_export_file(m_b, k, &pDev, &nLen, &nResult, &nDetail, &nFileInd) == 0; }
     bool     BatchReadExport(int k, std::vector<uint8_t>& file)

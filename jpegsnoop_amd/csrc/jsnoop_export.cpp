@@ -3,7 +3,7 @@
 #include <stdio.h>
 #include "jsnoop_host.h"
 #include "jsnoop_launch.h"
-#include "jsnoop_export_check.h"
+#include "jsnoop_export_opt_check.h"
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     js_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
@@ -26,29 +26,46 @@ static int js_export_q(void* user, int i, int comp, uint16_t* out64) { return js
 //   1. k_export_measure + k_export_scan; the result words and the bit length of every entry come back (wait 1): the host sizes the un-stuffed streams and the files.
 //   2. the streams zeroed, k_export_bits, k_export_ffcount, k_export_scan, k_export_stuff; the file lengths come back (wait 2).
 // (pack_block's wait for the event of the first copy, in front of phase 2, finds it complete: wait 1 was behind it.)
+// With JSNOOP_HUFFMAN_OPTIMAL (jsnoop_export_opt_check.h has the arithmetic) phase 1 is k_export_symbols, k_export_huff, k_export_measure with every entry's own
+// tables, k_export_scan; the header lengths come back with wait 1, and phase 2 reads tables and headers from d_export_opt, where the device built them (the second
+// copy of the call's block rewrites d_pack, so nothing the device made lives there).
 int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images, int n)
 {
+    JsnoopExportCoding coding; js_export_coding_defaults(&coding);
+    return export_jpeg_coded(spec_in, &coding, images, n);
+}
+int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const JsnoopExportCoding* coding_in, const int* images, int n)
+{
+    JsnoopExportCoding coding;
+    if (js_export_import_coding(coding_in, &coding)) return -1;
+    const bool opt = coding.huffman == JSNOOP_HUFFMAN_OPTIMAL;
     if (!uploaded || last_form == 0 || !dev.coef || !dev.dccum) { js_set_error("export_jpeg: the batch has not been decoded"); return -1; }
     JsnoopExportSpec spec;
     if (js_export_import_spec(spec_in, &spec)) return -1;
     if (n < 0) { js_set_error("export_jpeg: n = %d", n); return -1; }
     if (!images && (size_t)n > imgs.size()) { js_set_error("export_jpeg: n = %d without a list, the batch holds %zu", n, imgs.size()); return -1; }
-    exports.clear();
+    exports.clear(); export_opt = false;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(device));
-    const JsExportBlock blk = js_export_block((size_t)n);
+    const JsExportOptBlock oblk = js_export_opt_block((size_t)n);
+    const JsExportBlock blk = opt ? oblk.b : js_export_block((size_t)n);
     if (pack_block(blk.total)) return -1;
     JsExportRec* recs = reinterpret_cast<JsExportRec*>(h_pack + blk.recs);
     uint32_t* unit_base = reinterpret_cast<uint32_t*>(h_pack + blk.unit_base); uint32_t* chunk_base = reinterpret_cast<uint32_t*>(h_pack + blk.chunk_base);
     std::vector<uint8_t> unsupported((size_t)n);
     uint64_t blocks = 0;
-    if (js_export_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, unit_base, h_pack + blk.hdrs, unsupported.data(), &blocks)) return -1;
+    JsExportOptRec* orecs = opt ? reinterpret_cast<JsExportOptRec*>(h_pack + oblk.orecs) : nullptr;
+    if (opt ? js_export_opt_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, orecs, unit_base, h_pack + blk.hdrs, unsupported.data(), &blocks)
+            : js_export_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, unit_base, h_pack + blk.hdrs, unsupported.data(), &blocks)) return -1;
     memset(chunk_base, 0, ((size_t)n + 1) * 4);
     js_export_code_tabs(reinterpret_cast<uint32_t*>(h_pack + blk.tabs));
     if (ensure_generic()) return -1;
     const uint32_t units = unit_base[n];
-    const JsExportScratch sc = js_export_scratch((size_t)n, units, blocks);
+    const JsExportOptScratch osc = js_export_opt_scratch((size_t)n, units, blocks);
+    const JsExportScratch sc = opt ? osc.s : js_export_scratch((size_t)n, units, blocks);
+    const JsExportOptKeep keep = js_export_opt_keep((size_t)n);
     if (js_export_grow(&d_export_tmp, &d_export_tmp_cap, sc.total)) return -1;
+    if (opt && js_export_grow(&d_export_opt, &d_export_opt_cap, keep.total)) return -1;
     if (pack_send(blk.total)) return -1;
     HIP_TRY(hipMemsetAsync(d_export_tmp + sc.res, 0, (size_t)n * 4, stream));
     HIP_TRY(hipMemsetAsync(d_export_tmp + sc.res + (size_t)n * 4, 0xFF, (size_t)n * 8, stream));
@@ -56,7 +73,14 @@ int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images,
     const JsExportRec* d_recs = reinterpret_cast<const JsExportRec*>(d_pack + blk.recs);
     const uint32_t* d_unit_base = reinterpret_cast<const uint32_t*>(d_pack + blk.unit_base); const uint32_t* d_tabs = reinterpret_cast<const uint32_t*>(d_pack + blk.tabs);
     uint16_t* d_blk_bits = reinterpret_cast<uint16_t*>(d_export_tmp + sc.blk_bits); uint64_t* d_unit_off = reinterpret_cast<uint64_t*>(d_export_tmp + sc.unit_off);
-    if (js_launch_export_measure(stream, dev.coef, dev.dccum, d_recs, d_unit_base, (uint32_t)n, units, d_tabs, d_blk_bits, reinterpret_cast<uint32_t*>(d_export_tmp + sc.unit_bits),
+    if (opt) {
+        HIP_TRY(hipMemsetAsync(d_export_opt + keep.stats, 0, (size_t)n * sizeof(JsExportOptStat), stream));
+        if (js_launch_export_measure_opt(stream, dev.coef, dev.dccum, d_recs, reinterpret_cast<const JsExportOptRec*>(d_pack + oblk.orecs), d_unit_base, (uint32_t)n, units, d_tabs,
+                                         d_pack + blk.hdrs, reinterpret_cast<JsExportOptStat*>(d_export_opt + keep.stats), reinterpret_cast<uint32_t*>(d_export_opt + keep.tabs),
+                                         d_export_opt + keep.hdrs, reinterpret_cast<uint32_t*>(d_export_tmp + osc.hdr_len), d_blk_bits, reinterpret_cast<uint32_t*>(d_export_tmp + sc.unit_bits),
+                                         d_unit_off, reinterpret_cast<uint32_t*>(d_export_tmp + sc.res), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_bits))) {
+            js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
+    } else if (js_launch_export_measure(stream, dev.coef, dev.dccum, d_recs, d_unit_base, (uint32_t)n, units, d_tabs, d_blk_bits, reinterpret_cast<uint32_t*>(d_export_tmp + sc.unit_bits),
                                  d_unit_off, reinterpret_cast<uint32_t*>(d_export_tmp + sc.res), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_bits))) {
         js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
     std::vector<uint8_t> back(sc.len);
@@ -64,8 +88,10 @@ int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images,
     std::vector<int> result((size_t)n); std::vector<uint32_t> detail((size_t)n);
     uint64_t u_bytes = 0, out_bytes = 0;
     if (pack_block(blk.total)) return -1;
-    if (js_export_layout(recs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
-                         chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)) return -1;
+    if (opt ? js_export_opt_layout(recs, orecs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
+                                   reinterpret_cast<const uint32_t*>(back.data() + osc.hdr_len), chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)
+            : js_export_layout(recs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
+                               chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)) return -1;
     const uint32_t chunks = chunk_base[n];
     std::vector<uint64_t> len((size_t)n, 0);
     if (chunks) {
@@ -73,7 +99,11 @@ int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images,
         if (js_export_grow(&d_export_u, &d_export_u_cap, u_at + u_bytes) || js_export_grow(&d_export_out, &d_export_out_cap, out_bytes)) return -1;
         if (pack_send(blk.total)) return -1;
         HIP_TRY(hipMemsetAsync(d_export_u + u_at, 0, u_bytes, stream));
-        if (js_launch_export_write(stream, dev.coef, dev.dccum, d_recs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks, d_tabs,
+        if (opt ? js_launch_export_write_opt(stream, dev.coef, dev.dccum, d_recs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks,
+                                             reinterpret_cast<const uint32_t*>(d_export_opt + keep.tabs), d_blk_bits, d_unit_off, d_export_u + u_at, reinterpret_cast<uint32_t*>(d_export_u + ff_at),
+                                             reinterpret_cast<uint64_t*>(d_export_u + off_at), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_ff), d_export_opt + keep.hdrs, d_export_out,
+                                             reinterpret_cast<uint64_t*>(d_export_tmp + sc.len))
+                : js_launch_export_write(stream, dev.coef, dev.dccum, d_recs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks, d_tabs,
                                    d_blk_bits, d_unit_off, d_export_u + u_at, reinterpret_cast<uint32_t*>(d_export_u + ff_at), reinterpret_cast<uint64_t*>(d_export_u + off_at),
                                    reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_ff), d_pack + blk.hdrs, d_export_out, reinterpret_cast<uint64_t*>(d_export_tmp + sc.len))) {
             js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
@@ -84,6 +114,31 @@ int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images,
         if (recs[k].live && (e.len < recs[k].hdr_len + 3u || e.len > recs[k].out_cap)) {
             exports.clear(); js_set_error("export_jpeg: entry %d came back with %llu bytes, its place holds %llu", k, (unsigned long long)e.len, (unsigned long long)recs[k].out_cap); return -1; }
         exports.push_back(e);
+    }
+    export_opt = opt;
+    return 0;
+}
+
+int JsnoopBatch::export_tables(int k, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq)
+{
+    if (k < 0 || (size_t)k >= exports.size()) { js_set_error("export_tables: entry %d out of range, the last export holds %zu", k, exports.size()); return -1; }
+    if (!export_opt || !d_export_opt) { js_set_error("export_tables: the last export wrote the Annex K tables (huffman = 0): it built none"); return -1; }
+    const JsExportEntry& e = exports[(size_t)k];
+    if (e.result != JSNOOP_EXPORT_OK) { js_set_error("export_tables: entry %d was not exported (result %d): it has no tables", k, e.result); return -1; }
+    const int nslots = imgs[(size_t)e.image].ncomp == 1u ? 2 : 4;
+    if (slot < 0 || slot >= nslots) { js_set_error("export_tables: slot %d, image %d has slots 0 .. %d", slot, e.image, nslots - 1); return -1; }
+    HIP_TRY(hipSetDevice(device));
+    const JsExportOptKeep keep = js_export_opt_keep(exports.size());
+    std::vector<JsExportOptStat> st(1);
+    if (d2h_staged(st.data(), d_export_opt + keep.stats + (size_t)k * sizeof(JsExportOptStat), sizeof(JsExportOptStat))) return -1;
+    const JsExportOptSlot& s = st[0].slot[slot];
+    if (s.nsym > 256u) { js_set_error("export_tables: entry %d, slot %d came back with %u symbols", k, slot, s.nsym); return -1; }
+    if (counts) memcpy(counts, s.counts, 16);
+    if (symbols) memcpy(symbols, s.syms, 256);
+    if (nsym) *nsym = s.nsym;
+    if (freq) {
+        memset(freq, 0, 256 * 4);
+        if (slot & 1) memcpy(freq, st[0].freq + 32 + (slot >> 1) * 256, 256 * 4); else memcpy(freq, st[0].freq + (slot >> 1) * 16, 16 * 4);
     }
     return 0;
 }
@@ -146,7 +201,20 @@ int64_t jsnoop_batch_export_copy(JsnoopBatch* b, int k, void* dev_dst, uint64_t 
     HIP_TRY(hipMemcpyAsync(dev_dst, b->d_export_out + e->off, (size_t)e->len, hipMemcpyDeviceToDevice, b->stream));
     return (int64_t)e->len;
 }
-int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path)
+void jsnoop_export_coding_defaults(JsnoopExportCoding* out) { if (out) js_export_coding_defaults(out); }
+int jsnoop_batch_export_jpeg_coded(JsnoopBatch* b, const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const int* images, int n)
+{
+    if (!b) { js_set_error("export_jpeg: batch is NULL"); return -1; }
+    if (!coding) { js_set_error("export_jpeg: coding is NULL"); return -1; }
+    return b->export_jpeg_coded(spec, coding, images, n);
+}
+int jsnoop_batch_export_tables(JsnoopBatch* b, int k, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256])
+{
+    if (!b) { js_set_error("export_tables: batch is NULL"); return -1; }
+    return b->export_tables(k, slot, counts, symbols, nsym, freq);
+}
+int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path) { return jsnoop_export_jpeg_coded(d, path, nullptr); }
+int jsnoop_export_jpeg_coded(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding)
 {
     if (!d || !path) { js_set_error("jsnoop_export_jpeg: bad argument"); return -1; }
     if (!d->have_image || !d->preview_is_jpeg || !d->batch) { js_set_error("jsnoop_export_jpeg: no decoded image"); return -1; }
@@ -154,7 +222,7 @@ int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path)
     JsnoopBatch* b = d->batch;
     JsnoopExportSpec spec; js_export_spec_defaults(&spec);
     const int img = d->img;
-    if (b->export_jpeg(&spec, &img, 1)) return -1;
+    if (b->export_jpeg_coded(&spec, coding, &img, 1)) return -1;
     const JsExportEntry e = b->exports[0];
     if (e.result != JSNOOP_EXPORT_OK) { js_set_error("jsnoop_export_jpeg: not exported: %s, block %u", js_export_reason(e.result), e.detail); return -1; }
     std::vector<uint8_t> host((size_t)e.len);

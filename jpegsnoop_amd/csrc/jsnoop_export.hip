@@ -17,6 +17,11 @@
 //   k_export_ffcount  FF bytes of every JS_EXPORT_CHUNK-byte chunk of the un-stuffed streams.
 //   k_export_stuff    per chunk: an exclusive sum of the FF counts of 16-byte pieces, the stuffed bytes assembled in LDS, written out byte-coalesced at the
 //                     file's place; the first chunk's workgroup also copies the header the host built, the last one writes EOI and the file length.
+// With the images' own Huffman tables (jsnoop_batch_export_jpeg_coded, JSNOOP_HUFFMAN_OPTIMAL; the definition: tests/export_opt_model.py) two kernels run in front:
+//   k_export_symbols  the same walk with a sink that counts symbols: a tile histogram in LDS, added to the entry's 544 counters.
+//   k_export_huff     per entry, a wave per table: T.81 Annex K.2 (code sizes by merging groups, Adjust_BITS, the reserved code point, the symbol order, Annex C
+//                     codes), the entry's own code words and its header with the DHT segments it built.
+// and k_export_measure / k_export_bits read every entry's own code words (tab_stride words apart; 0: one set for all, the Annex K export).
 // Words of the bit stream are kept MSB-first as numbers and byte-swapped when they leave for memory.
 #include <hip/hip_runtime.h>
 #include "../../include/jsnoop_gpu.h"
@@ -51,7 +56,14 @@ __device__ __forceinline__ uint32_t ex_scan(uint32_t v, uint32_t* s, uint32_t* t
     return incl - v;
 }
 
-struct ExCount { uint32_t bits = 0; __device__ __forceinline__ void put(uint32_t, uint32_t n) { bits += n; } };
+// A sink of ex_walk sees every symbol twice: sym(class, symbol) -- class 0 DC, 1 AC -- and put(bits, count) with its code and value bits.
+struct ExCount { uint32_t bits = 0; __device__ __forceinline__ void put(uint32_t, uint32_t n) { bits += n; } __device__ __forceinline__ void sym(uint32_t, uint32_t) {} };
+// counts symbols into the tile's histogram in LDS (dc: 16 words, ac: 256 words of the block's table id)
+struct ExSymbols {
+    uint32_t* dc; uint32_t* ac;
+    __device__ __forceinline__ void put(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void sym(uint32_t cls, uint32_t s) { atomicAdd(cls ? ac + s : dc + s, 1u); }
+};
 // writes bit groups of at most 27 bits at a running position: into the LDS window where the word lies inside it, else into memory
 struct ExEmit {
     uint32_t* win; uint32_t* mem; uint64_t w0, pos;
@@ -66,6 +78,7 @@ struct ExEmit {
         else { const uint32_t k = off + n - 32u; word(w, v >> k); word(w + 1u, v << (32u - k)); }
         pos += n;
     }
+    __device__ __forceinline__ void sym(uint32_t, uint32_t) {}
 };
 
 // One AC value of a block: nothing but a longer run where its level is 0, else the ZRLs the run needs and the symbol (run, category) with the value bits
@@ -78,7 +91,8 @@ __device__ __forceinline__ void ex_coef(int32_t v, int32_t qz, uint32_t& run, bo
     if (!lv) { run++; return; }                                                     // (|v| < q: inexact, and no symbol)
     const uint32_t a = (uint32_t)(lv < 0 ? -lv : lv), cat = 32u - (uint32_t)__clz((int)a);
     uncodable |= a > 1023u;
-    while (run > 15u) { const uint32_t e = ac[0xF0]; sink.put(e & 0xFFFFu, e >> 16); run -= 16u; }
+    while (run > 15u) { const uint32_t e = ac[0xF0]; sink.sym(1u, 0xF0u); sink.put(e & 0xFFFFu, e >> 16); run -= 16u; }
+    sink.sym(1u, ((run << 4) | cat) & 255u);
     const uint32_t e = ac[((run << 4) | cat) & 255u], bits = (uint32_t)(lv < 0 ? lv - 1 : lv) & ((1u << cat) - 1u);
     sink.put(((e & 0xFFFFu) << cat) | bits, (e >> 16) + cat);
     run = 0;
@@ -95,6 +109,7 @@ __device__ __forceinline__ uint32_t ex_walk(const uint16_t* row, int32_t d, cons
         if (q0) { lv = d / q0; inexact |= lv * q0 != d; } else inexact |= d != 0;
         const uint32_t a = (uint32_t)(lv < 0 ? -lv : lv), cat = 32u - (uint32_t)__clz((int)a);
         uncodable |= a > 2047u;
+        sink.sym(0u, cat & 15u);
         const uint32_t e = dc[cat & 15u], bits = (uint32_t)(lv < 0 ? lv - 1 : lv) & ((1u << cat) - 1u);
         sink.put(((e & 0xFFFFu) << cat) | bits, (e >> 16) + cat);
     }
@@ -107,7 +122,7 @@ __device__ __forceinline__ uint32_t ex_walk(const uint16_t* row, int32_t d, cons
         ex_coef((int32_t)(int16_t)(two & 0xFFFFu), q[2u * w], run, inexact, uncodable, ac, sink);
         ex_coef((int32_t)two >> 16, q[2u * w + 1u], run, inexact, uncodable, ac, sink);
     }
-    if (run) { const uint32_t e = ac[0]; sink.put(e & 0xFFFFu, e >> 16); }
+    if (run) { const uint32_t e = ac[0]; sink.sym(1u, 0u); sink.put(e & 0xFFFFu, e >> 16); }
     return uncodable ? JSNOOP_EXPORT_UNCODABLE : (inexact ? JSNOOP_EXPORT_INEXACT : JSNOOP_EXPORT_OK);
 }
 
@@ -150,7 +165,7 @@ __device__ __forceinline__ int32_t ex_dc_diff(const int16_t* __restrict__ dccum,
 }
 
 __global__ void __launch_bounds__(EX_THREADS) k_export_measure(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
-                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs,
+                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, uint32_t tab_stride /*words from an entry's tables to the next's; 0: one set for all*/,
                                                                uint16_t* __restrict__ blk_bits, uint32_t* __restrict__ unit_bits, uint32_t* __restrict__ res /*[nrec] result, then [nrec][2] lowest block per kind*/)
 {
     __shared__ ExShared s;
@@ -160,7 +175,7 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_measure(const int16_t* __
     const uint32_t t0 = (unit - unit_base[k]) * JS_EXPORT_TILE, nblk = rp->nblk, nb = min(JS_EXPORT_TILE, nblk - t0), bpm = rp->bpm;
     const uint64_t coef_off = rp->coef_off;
     if (t == 0) { s_red[0] = 0u; s_red[1] = 0u; s_red[2] = 0xFFFFFFFFu; s_red[3] = 0xFFFFFFFFu; }
-    ex_stage(s, coef, *rp, t0, nb, tabs);
+    ex_stage(s, coef, *rp, t0, nb, tabs + (size_t)k * tab_stride);
     if (t < nb) {
         const uint32_t j = t0 + t; uint32_t c;
         const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, &c);
@@ -200,7 +215,7 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_scan(const uint32_t* __re
 }
 
 __global__ void __launch_bounds__(EX_THREADS) k_export_bits(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
-                                                            const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs,
+                                                            const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, uint32_t tab_stride,
                                                             const uint16_t* __restrict__ blk_bits, const uint64_t* __restrict__ unit_off, uint8_t* __restrict__ ustream)
 {
     __shared__ ExShared s;
@@ -212,7 +227,7 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_bits(const int16_t* __res
     const uint64_t coef_off = rp->coef_off, total_bits = rp->bits;
     uint32_t* mem = reinterpret_cast<uint32_t*>(ustream + rp->u_off);
     for (uint32_t i = t; i < EX_WIN_WORDS; i += EX_THREADS) s_win[i] = 0u;
-    ex_stage(s, coef, *rp, t0, nb, tabs);
+    ex_stage(s, coef, *rp, t0, nb, tabs + (size_t)k * tab_stride);
     uint32_t run_bits;
     const uint32_t mine = t < nb ? (uint32_t)blk_bits[rp->blk_base + t0 + t] : 0u, before = ex_scan(mine, s.scan, &run_bits);
     const uint64_t b0 = unit_off[unit];
@@ -298,22 +313,196 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_stuff(const JsExportRec* 
     if (lc + 1u == nchunks && t == 0u) { dst[n_out] = 0xFFu; dst[n_out + 1u] = 0xD9u; len[k] = (uint64_t)hdr_len + c0 + chunk_off[chunk] + n_out + 2u; }
 }
 
+// ---- JSNOOP_HUFFMAN_OPTIMAL: the symbol counts of every entry, and T.81 Annex K.2 per entry and table (the definition: tests/export_opt_model.py) ----
+// k_export_symbols: k_export_measure's geometry, the same walk with a sink that counts: LDS atomics into a tile histogram laid out like the code tables, the words
+// that are not zero added to the entry's (indices masked in ex_walk: an uncodable entry stays inside its 544 words).
+__global__ void __launch_bounds__(EX_THREADS) k_export_symbols(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
+                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, JsExportOptStat* __restrict__ stats)
+{
+    __shared__ ExShared s;
+    __shared__ uint32_t s_hist[JS_EXPORT_TAB_WORDS];
+    const uint32_t t = threadIdx.x, unit = blockIdx.x, k = ex_find(unit_base, nrec, unit);
+    const JsExportRec* rp = recs + k;
+    const uint32_t t0 = (unit - unit_base[k]) * JS_EXPORT_TILE, nblk = rp->nblk, nb = min(JS_EXPORT_TILE, nblk - t0), bpm = rp->bpm;
+    const uint64_t coef_off = rp->coef_off;
+    for (uint32_t i = t; i < JS_EXPORT_TAB_WORDS; i += EX_THREADS) s_hist[i] = 0u;
+    ex_stage(s, coef, *rp, t0, nb, tabs);
+    if (t < nb) {
+        uint32_t c;
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, t0 + t, &c);
+        const uint32_t tb = c ? 1u : 0u;
+        ExSymbols sink{ s_hist + tb * 16u, s_hist + 32u + tb * 256u };
+        ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
+    }
+    __syncthreads();
+    uint32_t* freq = stats[k].freq;
+    for (uint32_t i = t; i < JS_EXPORT_TAB_WORDS; i += EX_THREADS) { const uint32_t v = s_hist[i]; if (v) atomicAdd(freq + i, v); }
+}
+
+#define EX_HUFF_DEAD 0xFFFFFFFFFFFFFFFFull
+__device__ __forceinline__ uint64_t ex_wave_min(uint64_t v)
+{
+    #pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { const uint64_t o = __shfl_xor(v, d); v = o < v ? o : v; }
+    return v;
+}
+// k_export_huff: one workgroup per entry, wave w builds the table of slot w (2 * table id + class).  A lane holds symbols 5 * lane .. 5 * lane + 4 of the 257 (256: the
+// reserved one, frequency 1) in registers: the key (frequency << 9 | 511 - symbol) of a live group head -- the least key is the least frequency and, among equals,
+// the LARGEST symbol --, the code size and the group id.  A merge is two wave-wide minima and one step over the five: every symbol of group c1 or c2 gets one more
+// bit and the id c1 (what K.2's OTHERS chains do one link at a time).  Then lengths are counted, one lane runs Adjust_BITS (Figure K.3) and takes the reserved
+// code point off the longest length, the symbols are ranked by (code size, symbol) and get their Annex C codes.  The whole workgroup then puts the entry's header
+// together.  Every barrier is met by all four waves: a slot the image does not have runs along with nothing but the reserved symbol.
+__global__ void __launch_bounds__(EX_THREADS) k_export_huff(const JsExportRec* __restrict__ recs, const JsExportOptRec* __restrict__ orecs, const uint32_t* __restrict__ unit_base,
+                                                            const uint8_t* __restrict__ hdrs, JsExportOptStat* __restrict__ stats, uint32_t* __restrict__ tabs,
+                                                            uint8_t* __restrict__ hdr_out, uint32_t* __restrict__ hdr_len)
+{
+    __shared__ uint16_t s_size[4][264];                 // code size by symbol; 0xFFFF: the symbol does not occur
+    __shared__ uint32_t s_bits[4][264];                 // symbols by code size (0 .. 257)
+    __shared__ uint8_t s_syms[4][256];                  // symbols in code order
+    __shared__ uint32_t s_start[4][18], s_first[4][18]; // rank and code of the first symbol of every length 1 .. 16; s_start[w][17] = the number of symbols
+    const uint32_t t = threadIdx.x, k = blockIdx.x, w = t >> 6, lane = t & 63u;
+    if (unit_base[k + 1] == unit_base[k]) { if (t == 0) hdr_len[k] = 0u; return; }      // (an unsupported entry: nothing was counted)
+    const JsExportOptRec o = orecs[k];
+    const bool have = w < o.nslots;
+    const uint32_t cls = w & 1u, tb = w >> 1, nsymbols = cls ? 256u : 16u;
+    const uint32_t* freq = stats[k].freq + (cls ? 32u + tb * 256u : tb * 16u);
+    uint64_t key[5]; uint32_t size[5], group[5];
+    #pragma unroll
+    for (uint32_t e = 0; e < 5u; e++) {
+        const uint32_t sy = lane * 5u + e;
+        const uint64_t f = sy == 256u ? 1u : (have && sy < nsymbols ? (uint64_t)freq[sy] : 0u);
+        key[e] = f ? (f << 9 | (511u - sy)) : EX_HUFF_DEAD; size[e] = 0u; group[e] = f ? sy : 0xFFFFu;
+    }
+    for (;;) {
+        uint64_t m = key[0];
+        #pragma unroll
+        for (uint32_t e = 1; e < 5u; e++) m = key[e] < m ? key[e] : m;
+        const uint64_t m1 = ex_wave_min(m);
+        m = EX_HUFF_DEAD;
+        #pragma unroll
+        for (uint32_t e = 0; e < 5u; e++) m = key[e] != m1 && key[e] < m ? key[e] : m;
+        const uint64_t m2 = ex_wave_min(m);
+        if (m2 == EX_HUFF_DEAD) break;                              // one group left (the same in every lane)
+        const uint32_t c1 = 511u - (uint32_t)(m1 & 511u), c2 = 511u - (uint32_t)(m2 & 511u);
+        const uint64_t merged = ((m1 >> 9) + (m2 >> 9)) << 9 | (511u - c1);      // (sums in 64 bits: below 2^33)
+        #pragma unroll
+        for (uint32_t e = 0; e < 5u; e++) {
+            if (key[e] == m1) key[e] = merged; else if (key[e] == m2) key[e] = EX_HUFF_DEAD;
+            if (group[e] == c1 || group[e] == c2) { size[e]++; group[e] = c1; }
+        }
+    }
+    for (uint32_t i = lane; i < 264u; i += 64u) s_bits[w][i] = 0u;
+    #pragma unroll
+    for (uint32_t e = 0; e < 5u; e++) { const uint32_t sy = lane * 5u + e; if (sy < 264u) s_size[w][sy] = group[e] != 0xFFFFu ? (uint16_t)size[e] : (uint16_t)0xFFFFu; }
+    __syncthreads();
+    #pragma unroll
+    for (uint32_t e = 0; e < 5u; e++) if (group[e] != 0xFFFFu) atomicAdd(&s_bits[w][size[e] < 263u ? size[e] : 263u], 1u);
+    __syncthreads();
+    if (lane == 0u) {
+        uint32_t* bits = s_bits[w];
+        uint32_t i = 263u;
+        while (i > 0u && !bits[i]) i--;
+        bool sound = true;
+        while (i > 16u && sound) {                                  // Figure K.3
+            while (bits[i] > 0u) {
+                uint32_t j = i - 2u;
+                while (j > 0u && !bits[j]) j--;
+                if (!j || bits[i] < 2u) { sound = false; break; }   // (no code tree has such counts)
+                bits[i] -= 2u; bits[i - 1u] += 1u; bits[j + 1u] += 2u; bits[j] -= 1u;
+            }
+            i--;
+        }
+        while (i > 0u && !bits[i]) i--;
+        if (i) bits[i] -= 1u;                                       // the reserved code point
+        uint32_t code = 0u, at = 0u;
+        for (uint32_t ln = 1; ln <= 16u; ln++) { s_start[w][ln] = at; s_first[w][ln] = code; at += bits[ln]; code = (code + bits[ln]) << 1; }
+        s_start[w][17] = at < 256u ? at : 256u;
+    }
+    for (uint32_t i = lane; i < 256u; i += 64u) s_syms[w][i] = 0u;
+    __syncthreads();
+    uint32_t* my_tabs = tabs + (size_t)k * JS_EXPORT_TAB_WORDS + (cls ? 32u + tb * 256u : tb * 16u);
+    #pragma unroll
+    for (uint32_t e = 0; e < 5u; e++) {
+        const uint32_t sy = lane * 5u + e;
+        if (sy >= nsymbols) continue;
+        uint32_t word = 0u;
+        if (group[e] != 0xFFFFu) {
+            uint32_t rank = 0u;
+            for (uint32_t u = 0; u < nsymbols; u++) { const uint32_t su = s_size[w][u]; rank += (su < size[e] || (su == size[e] && u < sy)) ? 1u : 0u; }
+            uint32_t ln = 1u;
+            while (ln < 16u && s_start[w][ln + 1u] <= rank) ln++;
+            word = ln << 16 | ((s_first[w][ln] + rank - s_start[w][ln]) & 0xFFFFu);
+            s_syms[w][rank & 255u] = (uint8_t)sy;
+        }
+        my_tabs[sy] = word;
+    }
+    __syncthreads();
+    JsExportOptSlot* slot = stats[k].slot + w;
+    if (lane == 0u) slot->nsym = have ? s_start[w][17] : 0u;
+    if (lane < 16u) slot->counts[lane] = have ? (uint8_t)s_bits[w][lane + 1u] : (uint8_t)0u;
+    for (uint32_t i = lane; i < 256u; i += 64u) slot->syms[i] = have ? s_syms[w][i] : (uint8_t)0u;
+    // the header: the host's bytes up to SOF, a DHT segment per slot, the host's SOS
+    uint32_t seg_at[5]; seg_at[0] = o.pre_len;
+    #pragma unroll
+    for (uint32_t q = 0; q < 4u; q++) seg_at[q + 1u] = seg_at[q] + (q < o.nslots ? 21u + s_start[q][17] : 0u);
+    const uint32_t total = min(seg_at[4] + o.sos_len, JS_EXPORT_OPT_HDR);
+    const uint8_t* h = hdrs + recs[k].hdr_off; uint8_t* out = hdr_out + (size_t)k * JS_EXPORT_OPT_HDR;
+    for (uint32_t i = t; i < total; i += EX_THREADS) {
+        uint32_t b;
+        if (i < o.pre_len) b = h[i];
+        else if (i >= seg_at[4]) b = h[o.sos_off + (i - seg_at[4])];
+        else {
+            uint32_t q = 0u;
+            #pragma unroll
+            for (uint32_t r = 1; r < 4u; r++) q += i >= seg_at[r] ? 1u : 0u;
+            const uint32_t rel = i - seg_at[q], n = s_start[q][17];
+            b = rel == 0u ? 0xFFu : rel == 1u ? 0xC4u : rel == 2u ? (19u + n) >> 8 : rel == 3u ? (19u + n) & 255u : rel == 4u ? ((q & 1u) << 4 | q >> 1)
+              : rel < 21u ? s_bits[q][rel - 4u] : (uint32_t)s_syms[q][(rel - 21u) & 255u];
+        }
+        out[i] = (uint8_t)b;
+    }
+    if (t == 0u) hdr_len[k] = total;
+}
+
 int js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                              const uint32_t* tabs, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
 {
     if (!nrec) return 0;
-    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, blk_bits, unit_bits, res);
+    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, 0u, blk_bits, unit_bits, res);
     hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, unit_bits, unit_off, unit_base, ent_bits);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int js_launch_export_measure_opt(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportOptRec* orecs, const uint32_t* unit_base,
+                                 uint32_t nrec, uint32_t total_units, const uint32_t* annex_tabs, const uint8_t* hdrs, JsExportOptStat* stats, uint32_t* tabs, uint8_t* hdr_out,
+                                 uint32_t* hdr_len, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
+{
+    if (!nrec) return 0;
+    if (total_units) hipLaunchKernelGGL(k_export_symbols, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, annex_tabs, stats);
+    hipLaunchKernelGGL(k_export_huff, dim3(nrec), dim3(EX_THREADS), 0, st, recs, orecs, unit_base, hdrs, stats, tabs, hdr_out, hdr_len);
+    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, JS_EXPORT_TAB_WORDS, blk_bits, unit_bits, res);
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, unit_bits, unit_off, unit_base, ent_bits);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+static int ex_launch_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
+                           uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, uint32_t tab_stride, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
+                           uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
+{
+    if (!nrec || !total_units || !total_chunks) return 0;
+    hipLaunchKernelGGL(k_export_bits, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, tab_stride, blk_bits, unit_off, ustream);
+    hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_ff);
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, chunk_ff, chunk_off, chunk_base, ent_ff);
+    hipLaunchKernelGGL(k_export_stuff, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_off, hdrs, out, len);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int js_launch_export_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
                            uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
                            uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
 {
-    if (!nrec || !total_units || !total_chunks) return 0;
-    hipLaunchKernelGGL(k_export_bits, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, blk_bits, unit_off, ustream);
-    hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_ff);
-    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, chunk_ff, chunk_off, chunk_base, ent_ff);
-    hipLaunchKernelGGL(k_export_stuff, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_off, hdrs, out, len);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return ex_launch_write(st, coef, dccum, recs, unit_base, chunk_base, nrec, total_units, total_chunks, tabs, 0u, blk_bits, unit_off, ustream, chunk_ff, chunk_off, ent_ff, hdrs, out, len);
+}
+int js_launch_export_write_opt(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
+                               uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
+                               uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
+{
+    return ex_launch_write(st, coef, dccum, recs, unit_base, chunk_base, nrec, total_units, total_chunks, tabs, JS_EXPORT_TAB_WORDS, blk_bits, unit_off, ustream, chunk_ff, chunk_off, ent_ff, hdrs, out, len);
 }

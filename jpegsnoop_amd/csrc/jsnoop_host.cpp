@@ -308,6 +308,7 @@ JsnoopBatch::~JsnoopBatch()
     if (d_export_tmp) hipFree(d_export_tmp);
     if (d_export_u) hipFree(d_export_u);
     if (d_export_out) hipFree(d_export_out);
+    if (d_export_opt) hipFree(d_export_opt);
     if (ev_pack) hipEventDestroy(ev_pack);
     for (auto& e : ev) if (e) hipEventDestroy(e);
     for (auto& e : ev2) if (e) hipEventDestroy(e);

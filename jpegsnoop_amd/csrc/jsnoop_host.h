@@ -138,6 +138,12 @@ struct JsnoopBatch {
     int  pack_planes(const JsnoopPlaneSpec* spec, const int* images, int n, const JsnoopPlaneDst* dst);   // jsnoop_planes.cpp; the same block and event
     // jsnoop_batch_export_jpeg (jsnoop_export.cpp): the same block and event, two waits; the files live in d_export_out until the next export, clear, upload or destroy
     int  export_jpeg(const JsnoopExportSpec* spec, const int* images, int n);
+    // jsnoop_batch_export_jpeg_coded: huffman = JSNOOP_HUFFMAN_ANNEX_K is export_jpeg; JSNOOP_HUFFMAN_OPTIMAL counts the symbols of every entry and builds its
+    // tables and its header on the device in front of the first wait (d_export_opt: JsExportOptStat, code tables and headers per entry; export_opt says the last
+    // export left them there for export_tables, one staged copy on demand)
+    int  export_jpeg_coded(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const int* images, int n);
+    int  export_tables(int k, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq);
+    uint8_t* d_export_opt = nullptr; size_t d_export_opt_cap = 0; bool export_opt = false;
     struct JsExportEntry { uint64_t off, len; int result; uint32_t detail; int image; };   // entry k of the last export: its file at d_export_out + off
     std::vector<JsExportEntry> exports;
     uint8_t* d_export_tmp = nullptr; size_t d_export_tmp_cap = 0; // scratch of the first phase: result words, bit lengths per block / tile / entry

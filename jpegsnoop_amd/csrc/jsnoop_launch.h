@@ -122,6 +122,18 @@ int  js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t
 int  js_launch_export_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
                             uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
                             uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
+// jsnoop_batch_export_jpeg_coded with JSNOOP_HUFFMAN_OPTIMAL, first phase: k_export_symbols over every unit (the symbol counts of every entry into stats[k].freq,
+// zeroed by the caller), k_export_huff, one workgroup per entry (T.81 K.2 per slot: stats[k].slot, the entry's JS_EXPORT_TAB_WORDS code words at
+// tabs + k * JS_EXPORT_TAB_WORDS, its header -- the host's bytes up to SOF, the built DHT segments, the host's SOS -- in JS_EXPORT_OPT_HDR bytes at
+// hdr_out + k * JS_EXPORT_OPT_HDR and its length in hdr_len[k]; an entry without a unit gets length 0), then k_export_measure with the entry's own tables and
+// k_export_scan.  0, -1 on a launch error.
+int  js_launch_export_measure_opt(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportOptRec* orecs, const uint32_t* unit_base,
+                                  uint32_t nrec, uint32_t total_units, const uint32_t* annex_tabs, const uint8_t* hdrs, JsExportOptStat* stats, uint32_t* tabs, uint8_t* hdr_out,
+                                  uint32_t* hdr_len, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits);
+// ... second phase: js_launch_export_write with every entry's own code tables (tabs + k * JS_EXPORT_TAB_WORDS)
+int  js_launch_export_write_opt(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
+                                uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
+                                uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
 // jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
 // head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
 // the two totals as 64-bit words).  0, -1 on a launch error.

@@ -192,6 +192,16 @@ struct JsPlaneArgs { float scale[3], bias[3]; };
 #define JS_EXPORT_WINDOW 8192u       /* public: JSNOOP_EXPORT_WINDOW */
 struct JsExportRec { uint64_t coef_off, blk_base, bits, u_off, out_off, out_cap; uint32_t nblk, bpm, hdr_off, hdr_len, live, ncomp;
                      uint8_t comp[JS_MAX_BLK_PER_MCU], back[JS_MAX_BLK_PER_MCU]; uint16_t q[3][64]; };
+// jsnoop_batch_export_jpeg_coded with JSNOOP_HUFFMAN_OPTIMAL (k_export_symbols, k_export_huff): a side record per entry beside JsExportRec -- how the header the
+// host built splits around its DHT segments: [0, pre_len) ends behind SOF, [sos_off, sos_off + sos_len) is SOS; nslots: 2 (grey) or 4 tables -- and what the
+// device keeps per entry: the symbol counts (laid out like the code tables: DC0[16] DC1[16] AC0[256] AC1[256]) and, per slot (2 * table id + class), the
+// table it built (counts per length 1..16, symbols in code order, zero behind nsym).  The device assembles the entry's header in JS_EXPORT_OPT_HDR bytes of
+// its own: 438 bytes up to SOF at most, four DHT segments of at most 21 + 16 / 21 + 256 bytes (every counter of an uncodable entry), SOS 14.
+#define JS_EXPORT_OPT_HDR 1280u
+#define JS_EXPORT_OPT_MAX_BLOCKS (1u << 26)      /* at most 63 counts a block: uint32 counters hold below this many blocks */
+struct JsExportOptRec { uint32_t pre_len, sos_off, sos_len, nslots; };
+struct JsExportOptSlot { uint32_t nsym; uint8_t counts[16]; uint8_t syms[256]; };
+struct JsExportOptStat { uint32_t freq[544]; JsExportOptSlot slot[4]; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

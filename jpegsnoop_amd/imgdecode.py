@@ -83,10 +83,13 @@ class CimgDecode:
     def ExportTiff(self, path: str, nMode: int = 0) -> bool:
         return self._lib.jsnoop_export_tiff(self._h, path.encode(), nMode) == 0
 
-    def export_jpeg(self, path: str) -> bool:
+    def export_jpeg(self, path: str, huffman: str = "annex_k") -> bool:
         """The decoded image written back as a baseline JPEG file (jsnoop_export_jpeg): the coefficients the decoder holds, entropy-coded on the
-        device.  False, and no file, where the image cannot be exported (capi.last_error() has the reason)."""
-        return self._lib.jsnoop_export_jpeg(self._h, path.encode()) == 0
+        device.  False, and no file, where the image cannot be exported (capi.last_error() has the reason).  huffman="optimal": with the image's own
+        Huffman tables (jsnoop_export_jpeg_coded)."""
+        if huffman == "annex_k":
+            return self._lib.jsnoop_export_jpeg(self._h, path.encode()) == 0
+        return self._lib.jsnoop_export_jpeg_coded(self._h, path.encode(), C.byref(capi.export_coding(self._lib, huffman))) == 0
 
     # --- results ---------------------------------------------------------------------------
     def IsPreviewReady(self): return bool(self._lib.jsnoop_is_preview_ready(self._h))
@@ -832,7 +835,7 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_log(self._h, i, int(histo_en), int(stat_clip_en), int(quiet), cb, None), "batch_log")
         return out
 
-    def _export(self, images, jfif, what):
+    def _export(self, images, jfif, what, huffman="annex_k"):
         n_all = len(self)
         idx = list(range(n_all)) if images is None else [int(i) for i in images]
         for i in idx:
@@ -843,8 +846,24 @@ class JpegBatch:
         spec.jfif = 1 if jfif else 0
         self.sync()
         ind = (C.c_int * max(len(idx), 1))(*idx)
-        self._chk(self._lib.jsnoop_batch_export_jpeg(self._h, C.byref(spec), ind, len(idx)), "batch_export_jpeg")
+        if huffman == "annex_k":
+            self._chk(self._lib.jsnoop_batch_export_jpeg(self._h, C.byref(spec), ind, len(idx)), "batch_export_jpeg")
+        else:
+            self._chk(self._lib.jsnoop_batch_export_jpeg_coded(self._h, C.byref(spec), C.byref(capi.export_coding(self._lib, huffman)), ind, len(idx)), "batch_export_jpeg_coded")
         return self.export_results()
+
+    def export_tables(self, k):
+        """Entry k of the last export_jpeg(huffman="optimal"): one dict per slot (2 * table id + class; two for a grey image, else four) with freq (256
+        symbol counts), counts (codes per length 1..16) and symbols (in code order) of the table the device built and wrote (jsnoop_batch_export_tables)."""
+        res = self.export_results()
+        if not 0 <= k < len(res):
+            raise IndexError(f"export_tables: entry {k} out of range, the last export holds {len(res)}")
+        out = []
+        for slot in range(2 if self.info(res[k]["image"])["ncomp"] == 1 else 4):
+            counts, syms, freq, n = (C.c_uint8 * 16)(), (C.c_uint8 * 256)(), (C.c_uint32 * 256)(), C.c_uint32()
+            self._chk(self._lib.jsnoop_batch_export_tables(self._h, k, slot, counts, syms, C.byref(n), freq), "batch_export_tables")
+            out.append(dict(slot=slot, freq=list(freq), counts=list(counts), symbols=list(syms[:n.value])))
+        return out
 
     def export_results(self):
         """The entries of the last export_jpeg / export_jpeg_to_torch, in the order of its list: dicts with image, result (capi.EXPORT_OK / _INEXACT /
@@ -857,14 +876,15 @@ class JpegBatch:
             out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
         return out
 
-    def export_jpeg(self, images=None, jfif=True):
+    def export_jpeg(self, images=None, jfif=True, huffman="annex_k"):
         """What the batch holds for the listed images (None = all; any order, repeats allowed) written back as baseline JPEG files, entropy-coded on
         the device by ONE jsnoop_batch_export_jpeg: a list with the file's bytes per entry, None where the image could not be exported
         (export_results() says why).  An exported file decodes to the same coefficients; where the source was a clean file, to the same pixels.
         jfif=False leaves the APP0 segment out.  Calls sync() first (a damaged file is exported as repaired); behind a DC-only fast-form decode the
-        batch is decoded once more in the generic form."""
+        batch is decoded once more in the generic form.  huffman="optimal": every file with its own Huffman tables, built on the device from the
+        image's symbol counts (export_tables(k) returns them); "annex_k" (the default): the tables of T.81 Annex K."""
         files = []
-        for k, e in enumerate(self._export(images, jfif, "export_jpeg")):
+        for k, e in enumerate(self._export(images, jfif, "export_jpeg", huffman)):
             if not e["len"]:
                 files.append(None); continue
             buf = (C.c_uint8 * e["len"])()
@@ -874,12 +894,12 @@ class JpegBatch:
             files.append(bytes(buf))
         return files
 
-    def export_jpeg_to_torch(self, images=None, jfif=True):
+    def export_jpeg_to_torch(self, images=None, jfif=True, huffman="annex_k"):
         """export_jpeg, but the files stay on the device: a list with one uint8 tensor per entry (None where the image could not be exported), copied
         out of the batch's memory by jsnoop_batch_export_copy -- they outlive the next export."""
         import torch
         dev = torch.device("cuda", self.device())
-        res = self._export(images, jfif, "export_jpeg_to_torch")
+        res = self._export(images, jfif, "export_jpeg_to_torch", huffman)
         sizes = [-(-e["len"] // 16) * 16 for e in res]
         flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
         cur = torch.cuda.current_stream(dev)
