@@ -665,6 +665,33 @@ void         jsnoop_export_coding_defaults(JsnoopExportCoding* out);            
 int          jsnoop_batch_export_jpeg_coded(JsnoopBatch*, const JsnoopExportSpec*, const JsnoopExportCoding*, const int* images, int n);
 int          jsnoop_batch_export_tables(JsnoopBatch*, int k, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256]);
 int          jsnoop_export_jpeg_coded(JsnoopDecoder*, const char* path, const JsnoopExportCoding*);
+/* Restart intervals in the written files.  jsnoop_batch_export_jpeg_rst is jsnoop_batch_export_jpeg_coded with a third spec that gives every entry a
+ * restart interval Ri in MCUs (tests/export_rst_model.py is the definition, byte for byte; DESIGN.md section 4.16 the contract).  Ri = 0 writes the
+ * file of jsnoop_batch_export_jpeg_coded.  For Ri in 1 .. 65535: interval r holds MCUs [r Ri, min((r + 1) Ri, MCUs)) in decode order; the DC predecessor
+ * of every component is 0 at the start of every interval (the first block of a component in an interval codes (int16)dccum[b] itself), so a restart can
+ * make an image UNCODABLE or INEXACT that is OK without one (a cumulative DC level beyond +-2047, or a cumulative DC that wrapped int16 and is no multiple
+ * of its multiplier any more) -- the result word says so, it is no error of the call; the header carries FF DD 00 04 Ri directly in front of SOS (behind
+ * the last DHT, also when there is one interval only); every interval is coded on its own (padded with ones to a whole byte, every FF followed by 00) and
+ * FF D0+(r & 7) stands between interval r and r + 1, never stuffed.  With JSNOOP_HUFFMAN_OPTIMAL the symbol counts are those of the levels above.
+ *   JSNOOP_RESTART_NONE    no DRI, no markers (interval must be 0).
+ *   JSNOOP_RESTART_MCUS    Ri = interval (1 .. 65535).
+ *   JSNOOP_RESTART_ROWS    Ri = interval x the image's MCUs per MCU row (interval 1 .. 65535); an entry whose Ri comes out above 65535 is
+ *                          JSNOOP_EXPORT_UNSUPPORTED (host arithmetic: nothing is launched for it, no other entry is disturbed).
+ *   JSNOOP_RESTART_SOURCE  Ri = the interval the image was decoded with, 0 where it had none (interval must be 0).  For a progressive image this is what
+ *                          the header walk recorded: the DRI in force when the walk ended.
+ * struct_size is read like JsnoopExportSpec's; NULL coding or restart: the defaults.  Refused with -1 and a text, nothing launched: an unknown mode, an
+ * interval of 0 or above 65535 with MCUS or ROWS, a non-zero interval with NONE or SOURCE, non-zero reserved.  Accessors, waits, ownership and
+ * invalidation are those of jsnoop_batch_export_jpeg.  jsnoop_batch_export_restart: the Ri entry k of the last export was written with and the number of
+ * intervals of its file (0 where no file was written); either pointer may be NULL.  jsnoop_export_jpeg_rst: jsnoop_export_jpeg_coded with a restart spec. */
+#define JSNOOP_RESTART_NONE   0   /* no DRI, no markers: jsnoop_batch_export_jpeg_coded byte for byte            */
+#define JSNOOP_RESTART_MCUS   1   /* Ri = interval                                                               */
+#define JSNOOP_RESTART_ROWS   2   /* Ri = interval * mcu_xmax of the image (interval MCU rows)                   */
+#define JSNOOP_RESTART_SOURCE 3   /* Ri = the image's own rst_interval when it was decoded with one, else 0      */
+typedef struct JsnoopExportRestart { uint32_t struct_size; int32_t mode; uint32_t interval; uint32_t reserved; } JsnoopExportRestart;
+void         jsnoop_export_restart_defaults(JsnoopExportRestart* out);                         /* NONE, 0; NULL tolerated */
+int          jsnoop_batch_export_jpeg_rst(JsnoopBatch*, const JsnoopExportSpec*, const JsnoopExportCoding*, const JsnoopExportRestart*, const int* images, int n);
+int          jsnoop_batch_export_restart(const JsnoopBatch*, int k, uint32_t* ri, uint64_t* intervals);   /* what entry k of the last export was written with */
+int          jsnoop_export_jpeg_rst(JsnoopDecoder*, const char* path, const JsnoopExportCoding*, const JsnoopExportRestart*);
 
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and

@@ -158,6 +158,30 @@ def export_coding(lib, huffman):
     return c
 
 
+RESTART_NONE, RESTART_MCUS, RESTART_ROWS, RESTART_SOURCE = 0, 1, 2, 3
+
+
+class ExportRestart(C.Structure):
+    """JsnoopExportRestart of include/jsnoop_gpu.h: the restart interval jsnoop_batch_export_jpeg_rst writes every entry with."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("interval", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def export_restart(lib, restart):
+    """The JsnoopExportRestart of restart = 0 (none) | an int (MCUs) | ("rows", n) | "source".  Values are handed to the library as given: it refuses
+    an interval above 65535."""
+    r = ExportRestart()
+    lib.jsnoop_export_restart_defaults(C.byref(r))
+    if isinstance(restart, str) and restart == "source":
+        r.mode = RESTART_SOURCE
+    elif isinstance(restart, (tuple, list)) and len(restart) == 2 and restart[0] == "rows" and isinstance(restart[1], int) and not isinstance(restart[1], bool) and 0 <= restart[1] < 1 << 32:
+        r.mode = RESTART_ROWS; r.interval = restart[1]
+    elif isinstance(restart, int) and not isinstance(restart, bool) and 0 <= restart < 1 << 32:
+        r.mode = RESTART_MCUS if restart else RESTART_NONE; r.interval = restart
+    else:
+        raise ValueError('restart must be 0, a number of MCUs, ("rows", n) or "source", not %r' % (restart,))
+    return r
+
+
 CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
 CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
 CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
@@ -333,6 +357,10 @@ SIGNATURES = {
     "jsnoop_batch_export_jpeg_coded": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), _PI, _i]),
     "jsnoop_batch_export_tables": (_i, [_p, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "jsnoop_export_jpeg_coded": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding)]),
+    "jsnoop_export_restart_defaults": (None, [C.POINTER(ExportRestart)]),
+    "jsnoop_batch_export_jpeg_rst": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), C.POINTER(ExportRestart), _PI, _i]),
+    "jsnoop_batch_export_restart": (_i, [_p, _i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "jsnoop_export_jpeg_rst": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding), C.POINTER(ExportRestart)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

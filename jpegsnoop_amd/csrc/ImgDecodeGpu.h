@@ -133,6 +133,11 @@ public:
     // Export to TIFF (CJPEGsnoopDoc::OnToolsExporttiff + FileTiff::WriteFile): nMode 0 RGB8, 1 RGB16, 2 YCC8
     bool ExportTiff(const std::string& strFnameOut, int nMode) { return jsnoop_export_tiff(m_h, strFnameOut.c_str(), nMode) == 0; }
     bool ExportJpeg(const std::string& strFnameOut) { return jsnoop_export_jpeg(m_h, strFnameOut.c_str()) == 0; }   // the coefficients the decoder holds as a baseline JPEG file, coded on the device
+    // ... with restart intervals (jsnoop_export_jpeg_rst): nMode JSNOOP_RESTART_*, nInterval in MCUs or MCU rows; bOptimal: the image's own Huffman tables
+    bool ExportJpegRestart(const std::string& strFnameOut, bool bOptimal, int nMode, unsigned nInterval)
+    { JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = bOptimal ? JSNOOP_HUFFMAN_OPTIMAL : JSNOOP_HUFFMAN_ANNEX_K;
+      JsnoopExportRestart rst; jsnoop_export_restart_defaults(&rst); rst.mode = nMode; rst.interval = nInterval;
+      return jsnoop_export_jpeg_rst(m_h, strFnameOut.c_str(), &coding, &rst) == 0; }
     // hover helpers next to LookupFilePosMcu (source/JPEGsnoopViewImg.cpp:294-334); CPoint is a pair of unsigned here
     void PixelToMcu(unsigned nPixX, unsigned nPixY, unsigned& nMcuX, unsigned& nMcuY) { jsnoop_pixel_to_mcu(m_h, nPixX, nPixY, &nMcuX, &nMcuY); }               // :5056
     void PixelToBlk(unsigned nPixX, unsigned nPixY, unsigned& nBlkX, unsigned& nBlkY) { jsnoop_pixel_to_blk(m_h, nPixX, nPixY, &nBlkX, &nBlkY); }               // :5071
@@ -276,6 +281,14 @@ public:
       if (!bOptimal) return jsnoop_batch_export_jpeg(m_b, &spec, p, n) == 0;
       JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = JSNOOP_HUFFMAN_OPTIMAL;
       return jsnoop_batch_export_jpeg_coded(m_b, &spec, &coding, p, n) == 0; }
+    // BatchExportJpeg with a restart interval per file (jsnoop_batch_export_jpeg_rst): nMode JSNOOP_RESTART_*, nInterval in MCUs or MCU rows; BatchExportRestart: what entry k got
+    bool     BatchExportJpegRestart(const std::vector<int>& files, bool bJfif, bool bOptimal, int nMode, unsigned nInterval)
+    { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;
+      JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = bOptimal ? JSNOOP_HUFFMAN_OPTIMAL : JSNOOP_HUFFMAN_ANNEX_K;
+      JsnoopExportRestart rst; jsnoop_export_restart_defaults(&rst); rst.mode = nMode; rst.interval = nInterval;
+      const int n = files.empty() ? jsnoop_batch_count(m_b) : (int)files.size();
+      return jsnoop_batch_export_jpeg_rst(m_b, &spec, &coding, &rst, files.empty() ? nullptr : files.data(), n) == 0; }
+    bool     BatchExportRestart(int k, uint32_t& nRi, uint64_t& nIntervals) const { return jsnoop_batch_export_restart(m_b, k, &nRi, &nIntervals) == 0; }
     bool     BatchExportTables(int k, int nSlot, uint8_t anCounts[16], uint8_t anSymbols[256], uint32_t& nSymbols, uint32_t anFreq[256])
     { return jsnoop_batch_export_tables(m_b, k, nSlot, anCounts, anSymbols, &nSymbols, anFreq) == 0; }
     int      BatchExportCount() const { return jsnoop_batch_export_count(m_b); }

@@ -3,7 +3,7 @@
 #include <stdio.h>
 #include "jsnoop_host.h"
 #include "jsnoop_launch.h"
-#include "jsnoop_export_opt_check.h"
+#include "jsnoop_export_rst_check.h"
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     js_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
@@ -36,8 +36,17 @@ int JsnoopBatch::export_jpeg(const JsnoopExportSpec* spec_in, const int* images,
 }
 int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const JsnoopExportCoding* coding_in, const int* images, int n)
 {
+    return export_jpeg_rst(spec_in, coding_in, nullptr, images, n);
+}
+// With restart intervals (jsnoop_export_rst_check.h has the arithmetic) the plan gains the side records and DRI in the headers, phase 1 measures with the restart forms
+// (k_export_rst_scan in place of k_export_scan over the units) and phase 2 runs k_export_bits in its restart form, which fills the interval tables, and
+// k_export_stuff_rst; the interval tables live behind the first phase's scratch.  A call in which no entry has an interval takes none of this.
+int JsnoopBatch::export_jpeg_rst(const JsnoopExportSpec* spec_in, const JsnoopExportCoding* coding_in, const JsnoopExportRestart* restart_in, const int* images, int n)
+{
     JsnoopExportCoding coding;
     if (js_export_import_coding(coding_in, &coding)) return -1;
+    JsnoopExportRestart restart;
+    if (js_export_import_restart(restart_in, &restart)) return -1;
     const bool opt = coding.huffman == JSNOOP_HUFFMAN_OPTIMAL;
     if (!uploaded || last_form == 0 || !dev.coef || !dev.dccum) { js_set_error("export_jpeg: the batch has not been decoded"); return -1; }
     JsnoopExportSpec spec;
@@ -47,8 +56,15 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
     exports.clear(); export_opt = false;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(device));
-    const JsExportOptBlock oblk = js_export_opt_block((size_t)n);
-    const JsExportBlock blk = opt ? oblk.b : js_export_block((size_t)n);
+    bool rst = false;                                            // some listed entry is written with a restart interval (or refused for one too large)
+    if (restart.mode != JSNOOP_RESTART_NONE) for (int k = 0; k < n && !rst; k++) {
+        const int i = images ? images[k] : k;
+        if (i < 0 || (size_t)i >= imgs.size()) break;                // (the plan names it)
+        rst = js_export_rst_ri(restart, imgs[(size_t)i]) != 0u;
+    }
+    const JsExportRstBlock rblk = js_export_rst_block((size_t)n, opt);
+    const JsExportOptBlock oblk = rst ? rblk.o : js_export_opt_block((size_t)n);
+    const JsExportBlock blk = rst ? rblk.o.b : (opt ? oblk.b : js_export_block((size_t)n));
     if (pack_block(blk.total)) return -1;
     JsExportRec* recs = reinterpret_cast<JsExportRec*>(h_pack + blk.recs);
     uint32_t* unit_base = reinterpret_cast<uint32_t*>(h_pack + blk.unit_base); uint32_t* chunk_base = reinterpret_cast<uint32_t*>(h_pack + blk.chunk_base);
@@ -57,12 +73,16 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
     JsExportOptRec* orecs = opt ? reinterpret_cast<JsExportOptRec*>(h_pack + oblk.orecs) : nullptr;
     if (opt ? js_export_opt_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, orecs, unit_base, h_pack + blk.hdrs, unsupported.data(), &blocks)
             : js_export_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, unit_base, h_pack + blk.hdrs, unsupported.data(), &blocks)) return -1;
+    JsExportRstRec* rrecs = rst ? reinterpret_cast<JsExportRstRec*>(h_pack + rblk.rrecs) : nullptr;
+    std::vector<uint64_t> ri((size_t)n, 0); uint64_t intervals = 0;
+    if (rst && js_export_rst_plan(imgs.data(), restart, images, n, recs, orecs, rrecs, unit_base, h_pack + blk.hdrs, unsupported.data(), ri.data(), &blocks, &intervals)) return -1;
     memset(chunk_base, 0, ((size_t)n + 1) * 4);
     js_export_code_tabs(reinterpret_cast<uint32_t*>(h_pack + blk.tabs));
     if (ensure_generic()) return -1;
     const uint32_t units = unit_base[n];
-    const JsExportOptScratch osc = js_export_opt_scratch((size_t)n, units, blocks);
-    const JsExportScratch sc = opt ? osc.s : js_export_scratch((size_t)n, units, blocks);
+    const JsExportRstScratch rsc = js_export_rst_scratch((size_t)n, units, blocks, intervals, opt);
+    const JsExportOptScratch osc = rst ? rsc.o : js_export_opt_scratch((size_t)n, units, blocks);
+    const JsExportScratch sc = rst ? rsc.o.s : (opt ? osc.s : js_export_scratch((size_t)n, units, blocks));
     const JsExportOptKeep keep = js_export_opt_keep((size_t)n);
     if (js_export_grow(&d_export_tmp, &d_export_tmp_cap, sc.total)) return -1;
     if (opt && js_export_grow(&d_export_opt, &d_export_opt_cap, keep.total)) return -1;
@@ -73,8 +93,16 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
     const JsExportRec* d_recs = reinterpret_cast<const JsExportRec*>(d_pack + blk.recs);
     const uint32_t* d_unit_base = reinterpret_cast<const uint32_t*>(d_pack + blk.unit_base); const uint32_t* d_tabs = reinterpret_cast<const uint32_t*>(d_pack + blk.tabs);
     uint16_t* d_blk_bits = reinterpret_cast<uint16_t*>(d_export_tmp + sc.blk_bits); uint64_t* d_unit_off = reinterpret_cast<uint64_t*>(d_export_tmp + sc.unit_off);
-    if (opt) {
-        HIP_TRY(hipMemsetAsync(d_export_opt + keep.stats, 0, (size_t)n * sizeof(JsExportOptStat), stream));
+    const JsExportRstRec* d_rrecs = rst ? reinterpret_cast<const JsExportRstRec*>(d_pack + rblk.rrecs) : nullptr;
+    if (opt) HIP_TRY(hipMemsetAsync(d_export_opt + keep.stats, 0, (size_t)n * sizeof(JsExportOptStat), stream));
+    if (rst) {
+        if (js_launch_export_measure_rst(stream, dev.coef, dev.dccum, d_recs, opt ? reinterpret_cast<const JsExportOptRec*>(d_pack + oblk.orecs) : nullptr, d_rrecs, d_unit_base, (uint32_t)n, units,
+                                         d_tabs, d_pack + blk.hdrs, opt ? reinterpret_cast<JsExportOptStat*>(d_export_opt + keep.stats) : nullptr,
+                                         opt ? reinterpret_cast<uint32_t*>(d_export_opt + keep.tabs) : nullptr, opt ? d_export_opt + keep.hdrs : nullptr,
+                                         opt ? reinterpret_cast<uint32_t*>(d_export_tmp + osc.hdr_len) : nullptr, d_blk_bits, reinterpret_cast<JsRstSum*>(d_export_tmp + rsc.sums), d_unit_off,
+                                         reinterpret_cast<uint32_t*>(d_export_tmp + sc.res), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_bits))) {
+            js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
+    } else if (opt) {
         if (js_launch_export_measure_opt(stream, dev.coef, dev.dccum, d_recs, reinterpret_cast<const JsExportOptRec*>(d_pack + oblk.orecs), d_unit_base, (uint32_t)n, units, d_tabs,
                                          d_pack + blk.hdrs, reinterpret_cast<JsExportOptStat*>(d_export_opt + keep.stats), reinterpret_cast<uint32_t*>(d_export_opt + keep.tabs),
                                          d_export_opt + keep.hdrs, reinterpret_cast<uint32_t*>(d_export_tmp + osc.hdr_len), d_blk_bits, reinterpret_cast<uint32_t*>(d_export_tmp + sc.unit_bits),
@@ -88,7 +116,9 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
     std::vector<int> result((size_t)n); std::vector<uint32_t> detail((size_t)n);
     uint64_t u_bytes = 0, out_bytes = 0;
     if (pack_block(blk.total)) return -1;
-    if (opt ? js_export_opt_layout(recs, orecs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
+    if (rst ? js_export_rst_layout(recs, orecs, rrecs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
+                                   opt ? reinterpret_cast<const uint32_t*>(back.data() + osc.hdr_len) : nullptr, chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)
+      : opt ? js_export_opt_layout(recs, orecs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
                                    reinterpret_cast<const uint32_t*>(back.data() + osc.hdr_len), chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)
             : js_export_layout(recs, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.ent_bits),
                                chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)) return -1;
@@ -99,7 +129,12 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
         if (js_export_grow(&d_export_u, &d_export_u_cap, u_at + u_bytes) || js_export_grow(&d_export_out, &d_export_out_cap, out_bytes)) return -1;
         if (pack_send(blk.total)) return -1;
         HIP_TRY(hipMemsetAsync(d_export_u + u_at, 0, u_bytes, stream));
-        if (opt ? js_launch_export_write_opt(stream, dev.coef, dev.dccum, d_recs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks,
+        if (rst ? js_launch_export_write_rst(stream, dev.coef, dev.dccum, d_recs, d_rrecs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks,
+                                             opt ? reinterpret_cast<const uint32_t*>(d_export_opt + keep.tabs) : d_tabs, opt ? JS_EXPORT_TAB_WORDS : 0u, d_blk_bits, d_unit_off,
+                                             reinterpret_cast<uint64_t*>(d_export_tmp + rsc.itab), d_export_u + u_at, reinterpret_cast<uint32_t*>(d_export_u + ff_at),
+                                             reinterpret_cast<uint64_t*>(d_export_u + off_at), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_ff), opt ? d_export_opt + keep.hdrs : d_pack + blk.hdrs,
+                                             d_export_out, reinterpret_cast<uint64_t*>(d_export_tmp + sc.len))
+          : opt ? js_launch_export_write_opt(stream, dev.coef, dev.dccum, d_recs, d_unit_base, reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, units, chunks,
                                              reinterpret_cast<const uint32_t*>(d_export_opt + keep.tabs), d_blk_bits, d_unit_off, d_export_u + u_at, reinterpret_cast<uint32_t*>(d_export_u + ff_at),
                                              reinterpret_cast<uint64_t*>(d_export_u + off_at), reinterpret_cast<uint64_t*>(d_export_tmp + sc.ent_ff), d_export_opt + keep.hdrs, d_export_out,
                                              reinterpret_cast<uint64_t*>(d_export_tmp + sc.len))
@@ -111,6 +146,7 @@ int JsnoopBatch::export_jpeg_coded(const JsnoopExportSpec* spec_in, const Jsnoop
     }
     for (int k = 0; k < n; k++) {
         JsExportEntry e; e.off = recs[k].out_off; e.len = recs[k].live ? len[k] : 0; e.result = result[k]; e.detail = detail[k]; e.image = images ? images[k] : k;
+        e.ri = (uint32_t)ri[(size_t)k]; e.intervals = recs[k].live ? (rst ? rrecs[k].ni : 1u) : 0u;
         if (recs[k].live && (e.len < recs[k].hdr_len + 3u || e.len > recs[k].out_cap)) {
             exports.clear(); js_set_error("export_jpeg: entry %d came back with %llu bytes, its place holds %llu", k, (unsigned long long)e.len, (unsigned long long)recs[k].out_cap); return -1; }
         exports.push_back(e);
@@ -148,7 +184,7 @@ static const char* js_export_reason(int result)
     switch (result) {
     case JSNOOP_EXPORT_INEXACT: return "a value is no multiple of its quantiser (INEXACT)";
     case JSNOOP_EXPORT_UNCODABLE: return "a level has no Annex K code (UNCODABLE)";
-    case JSNOOP_EXPORT_UNSUPPORTED: return "the sample precision is not 8 (UNSUPPORTED)";
+    case JSNOOP_EXPORT_UNSUPPORTED: return "the sample precision is not 8, or the restart interval is above 65535 (UNSUPPORTED)";
     default: return "ok";
     }
 }
@@ -213,8 +249,23 @@ int jsnoop_batch_export_tables(JsnoopBatch* b, int k, int slot, uint8_t counts[1
     if (!b) { js_set_error("export_tables: batch is NULL"); return -1; }
     return b->export_tables(k, slot, counts, symbols, nsym, freq);
 }
-int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path) { return jsnoop_export_jpeg_coded(d, path, nullptr); }
-int jsnoop_export_jpeg_coded(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding)
+void jsnoop_export_restart_defaults(JsnoopExportRestart* out) { if (out) js_export_restart_defaults(out); }
+int jsnoop_batch_export_jpeg_rst(JsnoopBatch* b, const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const int* images, int n)
+{
+    if (!b) { js_set_error("export_jpeg: batch is NULL"); return -1; }
+    return b->export_jpeg_rst(spec, coding, restart, images, n);
+}
+int jsnoop_batch_export_restart(const JsnoopBatch* b, int k, uint32_t* ri, uint64_t* intervals)
+{
+    const JsExportEntry* e = js_export_entry(b, k, "export_restart");
+    if (!e) return -1;
+    if (ri) *ri = e->ri;
+    if (intervals) *intervals = e->intervals;
+    return 0;
+}
+int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path) { return jsnoop_export_jpeg_rst(d, path, nullptr, nullptr); }
+int jsnoop_export_jpeg_coded(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding) { return jsnoop_export_jpeg_rst(d, path, coding, nullptr); }
+int jsnoop_export_jpeg_rst(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart)
 {
     if (!d || !path) { js_set_error("jsnoop_export_jpeg: bad argument"); return -1; }
     if (!d->have_image || !d->preview_is_jpeg || !d->batch) { js_set_error("jsnoop_export_jpeg: no decoded image"); return -1; }
@@ -222,7 +273,7 @@ int jsnoop_export_jpeg_coded(JsnoopDecoder* d, const char* path, const JsnoopExp
     JsnoopBatch* b = d->batch;
     JsnoopExportSpec spec; js_export_spec_defaults(&spec);
     const int img = d->img;
-    if (b->export_jpeg_coded(&spec, coding, &img, 1)) return -1;
+    if (b->export_jpeg_rst(&spec, coding, restart, &img, 1)) return -1;
     const JsExportEntry e = b->exports[0];
     if (e.result != JSNOOP_EXPORT_OK) { js_set_error("jsnoop_export_jpeg: not exported: %s, block %u", js_export_reason(e.result), e.detail); return -1; }
     std::vector<uint8_t> host((size_t)e.len);

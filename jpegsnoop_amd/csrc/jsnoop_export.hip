@@ -22,10 +22,19 @@
 //   k_export_huff     per entry, a wave per table: T.81 Annex K.2 (code sizes by merging groups, Adjust_BITS, the reserved code point, the symbol order, Annex C
 //                     codes), the entry's own code words and its header with the DHT segments it built.
 // and k_export_measure / k_export_bits read every entry's own code words (tab_stride words apart; 0: one set for all, the Annex K export).
+// With restart intervals (jsnoop_batch_export_jpeg_rst; the definition: tests/export_rst_model.py; arithmetic and the scan operator: jsnoop_export_rst_check.h)
+// k_export_measure, k_export_symbols and k_export_bits run in their RST form -- a template parameter: the plain instantiations are the code they were -- and two kernels
+// take the place of their plain siblings:
+//   the RST forms      the DC predecessor is 0 at every interval start (ex_dc_diff); an interval starts on a byte, so blocks are placed by a segmented scan of run
+//                      summaries (JsRstSum, js_rst_combine) in place of the plain sums; the thread of an interval's last block appends its padding ones and writes the
+//                      interval's end into the entry's interval table.
+//   k_export_rst_scan  k_export_scan over the tiles' summaries, a 64-bit bit position as the carry.
+//   k_export_stuff_rst k_export_stuff that finds the interval of its bytes in the interval table and writes FF D0+(r & 7) behind the last byte of interval r.
 // Words of the bit stream are kept MSB-first as numbers and byte-swapped when they leave for memory.
 #include <hip/hip_runtime.h>
 #include "../../include/jsnoop_gpu.h"
 #include "jsnoop_launch.h"
+#include "jsnoop_export_rst_check.h"
 
 #define EX_THREADS 256
 #define EX_ROW_HALVES 66u                             /* 132 bytes: 33 dwords */
@@ -127,7 +136,7 @@ __device__ __forceinline__ uint32_t ex_walk(const uint16_t* row, int32_t d, cons
 }
 
 struct ExShared {
-    uint16_t rows[JS_EXPORT_TILE * EX_ROW_HALVES];
+    union { uint16_t rows[JS_EXPORT_TILE * EX_ROW_HALVES]; JsRstSum sums[EX_THREADS]; };      // sums: k_export_measure's restart form, behind the walks
     uint16_t q[3][64];
     uint32_t dc[2][16], ac[2][256];
     uint32_t scan[EX_THREADS];
@@ -155,18 +164,40 @@ __device__ __forceinline__ void ex_stage(ExShared& s, const int16_t* __restrict_
     s.ac[0][t] = tabs[32u + t]; s.ac[1][t] = tabs[288u + t];
     __syncthreads();
 }
-// what block j of the entry is: its component (0-based) and its DC difference
-__device__ __forceinline__ int32_t ex_dc_diff(const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ rp, uint64_t coef_off, uint32_t bpm, uint32_t j, uint32_t* comp)
+// what block j of the entry is: its component (0-based) and its DC difference.  rb: the entry's restart interval in blocks (0: none) -- a predecessor in an
+// earlier interval counts as 0, so the first block of a component in an interval codes its cumulative value itself
+__device__ __forceinline__ int32_t ex_dc_diff(const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ rp, uint64_t coef_off, uint32_t bpm, uint32_t j, uint32_t rb, uint32_t* comp)
 {
     const uint32_t pos = j % bpm, back = rp->back[pos];
     *comp = rp->comp[pos];
-    const int32_t cur = dccum[coef_off + j], prev = j >= back ? (int32_t)dccum[coef_off + j - back] : 0;
+    const bool have = j >= back && (rb == 0u || j % rb >= back);
+    const int32_t cur = dccum[coef_off + j], prev = have ? (int32_t)dccum[coef_off + j - back] : 0;
     return (int32_t)(int16_t)(cur - prev);
 }
+// exclusive scan of run summaries over the workgroup with js_rst_combine; *total = the summary of all.  s: EX_THREADS summaries of LDS (free to reuse behind the call).
+__device__ __forceinline__ JsRstSum ex_rst_scan(JsRstSum v, JsRstSum* s, JsRstSum* total)
+{
+    const uint32_t t = threadIdx.x;
+    s[t] = v; __syncthreads();
+    for (uint32_t d = 1; d < EX_THREADS; d <<= 1) {
+        JsRstSum a = s[t];
+        if (t >= d) a = js_rst_combine(s[t - d], a);
+        __syncthreads();
+        s[t] = a; __syncthreads();
+    }
+    const JsRstSum ex = t ? s[t - 1u] : js_rst_identity();
+    *total = s[EX_THREADS - 1]; __syncthreads();
+    return ex;
+}
+// block j is the last of its interval (the entry's last block always is)
+__device__ __forceinline__ bool ex_rst_ends(uint32_t j, uint32_t nblk, uint32_t rb) { return j + 1u == nblk || (rb && (j + 1u) % rb == 0u); }
 
+// RST (jsnoop_batch_export_jpeg_rst; the definition: tests/export_rst_model.py): the DC predecessor is 0 at every interval start, and a unit's sum is a JsRstSum
+template <bool RST>
 __global__ void __launch_bounds__(EX_THREADS) k_export_measure(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
                                                                const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, uint32_t tab_stride /*words from an entry's tables to the next's; 0: one set for all*/,
-                                                               uint16_t* __restrict__ blk_bits, uint32_t* __restrict__ unit_bits, uint32_t* __restrict__ res /*[nrec] result, then [nrec][2] lowest block per kind*/)
+                                                               uint16_t* __restrict__ blk_bits, uint32_t* __restrict__ unit_bits, uint32_t* __restrict__ res /*[nrec] result, then [nrec][2] lowest block per kind*/,
+                                                               const JsExportRstRec* __restrict__ rrecs, JsRstSum* __restrict__ unit_sum /*both: RST only*/)
 {
     __shared__ ExShared s;
     __shared__ uint32_t s_red[4];                                 // sum of bits, result, lowest inexact block, lowest uncodable block
@@ -174,21 +205,30 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_measure(const int16_t* __
     const JsExportRec* rp = recs + k;
     const uint32_t t0 = (unit - unit_base[k]) * JS_EXPORT_TILE, nblk = rp->nblk, nb = min(JS_EXPORT_TILE, nblk - t0), bpm = rp->bpm;
     const uint64_t coef_off = rp->coef_off;
+    uint32_t rb = 0u;
+    if constexpr (RST) rb = rrecs[k].ri_blocks;
+    uint32_t my_bits = 0u; bool my_end = false;                      // (RST: this thread's leaf; a thread without a block has the identity)
     if (t == 0) { s_red[0] = 0u; s_red[1] = 0u; s_red[2] = 0xFFFFFFFFu; s_red[3] = 0xFFFFFFFFu; }
     ex_stage(s, coef, *rp, t0, nb, tabs + (size_t)k * tab_stride);
     if (t < nb) {
         const uint32_t j = t0 + t; uint32_t c;
-        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, &c);
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, rb, &c);
         const uint32_t tb = c ? 1u : 0u;
         ExCount sink;
         const uint32_t st = ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
         blk_bits[rp->blk_base + j] = (uint16_t)sink.bits;
-        atomicAdd(&s_red[0], sink.bits);
+        if constexpr (RST) { my_bits = sink.bits; my_end = ex_rst_ends(j, nblk, rb); } else atomicAdd(&s_red[0], sink.bits);
         if (st) { atomicMax(&s_red[1], st); atomicMin(&s_red[1u + st], j); }
+    }
+    if constexpr (RST) {
+        __syncthreads();                                              // every walk is done: the summaries are scanned where the tile's rows lay
+        JsRstSum all;
+        ex_rst_scan(js_rst_leaf(my_bits, my_end), s.sums, &all);
+        if (t == 0) { JsRstSum* o = unit_sum + unit; o->has = all.has; o->head = all.head; o->mid = all.mid; o->tail = all.tail; }
     }
     __syncthreads();
     if (t == 0) {
-        unit_bits[unit] = s_red[0];
+        if constexpr (!RST) unit_bits[unit] = s_red[0];
         if (s_red[1]) {
             atomicMax(res + k, s_red[1]);
             if (s_red[2] != 0xFFFFFFFFu) atomicMin(res + nrec + 2u * k, s_red[2]);
@@ -214,9 +254,32 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_scan(const uint32_t* __re
     if (t == 0) total[k] = carry;
 }
 
+// k_export_scan for the units of a call with restart intervals: the bit position of every unit's first block (off[i]) from the units' summaries, JS_EXPORT_SCAN at a
+// time with js_rst_combine in place of the sum and a 64-bit position as the carry; total[k]: the length of the entry's stream in bits (every interval padded, so
+// a multiple of 8: the entry's last block ends an interval)
+__global__ void __launch_bounds__(EX_THREADS) k_export_rst_scan(const JsRstSum* __restrict__ sum, uint64_t* __restrict__ off, const uint32_t* __restrict__ base, uint64_t* __restrict__ total)
+{
+    __shared__ JsRstSum s[EX_THREADS];
+    const uint32_t t = threadIdx.x, k = blockIdx.x, a = base[k], e = base[k + 1];
+    uint64_t carry = 0;
+    for (uint32_t i0 = a; i0 < e; i0 += JS_EXPORT_SCAN) {           // (a, e, i0: the same in every thread -- the barriers inside ex_rst_scan are met by all)
+        const uint32_t i = i0 + t; const bool mine = i < e && i >= i0;
+        JsRstSum step;
+        const JsRstSum ex = ex_rst_scan(mine ? sum[i] : js_rst_identity(), s, &step);
+        if (mine) off[i] = js_rst_apply(carry, ex);
+        carry = js_rst_apply(carry, step);
+        if (e - i0 <= JS_EXPORT_SCAN) break;                        // (i0 + JS_EXPORT_SCAN must not wrap)
+    }
+    if (t == 0) total[k] = carry;
+}
+
+// RST: blocks are placed by the summaries (an interval starts on a byte), the thread that owns the last block of an interval appends its padding ones and writes the
+// interval's end, in bytes, into the entry's interval table -- the entry's end is the last case of that rule
+template <bool RST>
 __global__ void __launch_bounds__(EX_THREADS) k_export_bits(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
                                                             const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, uint32_t tab_stride,
-                                                            const uint16_t* __restrict__ blk_bits, const uint64_t* __restrict__ unit_off, uint8_t* __restrict__ ustream)
+                                                            const uint16_t* __restrict__ blk_bits, const uint64_t* __restrict__ unit_off, uint8_t* __restrict__ ustream,
+                                                            const JsExportRstRec* __restrict__ rrecs, uint64_t* __restrict__ itab /*both: RST only*/)
 {
     __shared__ ExShared s;
     __shared__ uint32_t s_win[EX_WIN_WORDS];
@@ -228,21 +291,35 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_bits(const int16_t* __res
     uint32_t* mem = reinterpret_cast<uint32_t*>(ustream + rp->u_off);
     for (uint32_t i = t; i < EX_WIN_WORDS; i += EX_THREADS) s_win[i] = 0u;
     ex_stage(s, coef, *rp, t0, nb, tabs + (size_t)k * tab_stride);
-    uint32_t run_bits;
-    const uint32_t mine = t < nb ? (uint32_t)blk_bits[rp->blk_base + t0 + t] : 0u, before = ex_scan(mine, s.scan, &run_bits);
+    const uint32_t mine = t < nb ? (uint32_t)blk_bits[rp->blk_base + t0 + t] : 0u;
     const uint64_t b0 = unit_off[unit];
-    uint64_t b1 = b0 + run_bits;                                    // the range this workgroup writes: [b0, b1)
-    const bool last_unit = t0 + nb == nblk;
-    const uint32_t pad = (uint32_t)(0u - total_bits) & 7u;          // ones behind the entry's last block, up to a whole byte
-    if (last_unit) b1 += pad;
+    uint64_t b1, at;                                                // the range this workgroup writes: [b0, b1); where this thread's block starts
+    uint32_t pad, rb = 0u; bool pads;                               // ones behind this thread's block, up to a whole byte
+    if constexpr (RST) {
+        __shared__ JsRstSum s_sum[EX_THREADS];
+        rb = rrecs[k].ri_blocks;
+        const bool ends = t < nb && ex_rst_ends(t0 + t, nblk, rb);
+        JsRstSum all;
+        const JsRstSum ex = ex_rst_scan(t < nb ? js_rst_leaf(mine, ends) : js_rst_identity(), s_sum, &all);
+        at = js_rst_apply(b0, ex); b1 = js_rst_apply(b0, all);
+        pads = ends; pad = (uint32_t)(0u - (at + mine)) & 7u;
+    } else {
+        uint32_t run_bits;
+        const uint32_t before = ex_scan(mine, s.scan, &run_bits);
+        at = b0 + before; b1 = b0 + run_bits;
+        pad = (uint32_t)(0u - total_bits) & 7u;                     // behind the entry's last block
+        if (t0 + nb == nblk) b1 += pad;
+        pads = t0 + t + 1u == nblk;
+    }
     const uint64_t w0 = b0 >> 5, wl = (b1 - 1u) >> 5;               // first and last word of the range (every block has bits: b1 > b0)
     if (t < nb) {
         const uint32_t j = t0 + t; uint32_t c;
-        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, &c);
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, j, rb, &c);
         const uint32_t tb = c ? 1u : 0u;
-        ExEmit sink{ s_win, mem, w0, b0 + before };
+        ExEmit sink{ s_win, mem, w0, at };
         ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
-        if (j + 1u == nblk && pad) sink.put((1u << pad) - 1u, pad);
+        if (pads && pad) sink.put((1u << pad) - 1u, pad);
+        if constexpr (RST) { if (pads) itab[rrecs[k].itab_off + (rb ? j / rb : 0u)] = (at + mine + pad) >> 3; }
     }
     __syncthreads();
     const uint64_t nw = wl - w0 + 1u;
@@ -313,11 +390,64 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_stuff(const JsExportRec* 
     if (lc + 1u == nchunks && t == 0u) { dst[n_out] = 0xFFu; dst[n_out + 1u] = 0xD9u; len[k] = (uint64_t)hdr_len + c0 + chunk_off[chunk] + n_out + 2u; }
 }
 
+// k_export_stuff for a call with restart intervals.  The un-stuffed stream holds the padded intervals and no marker; byte p of interval r goes to header + p +
+// (FFs in front of p) + 2 r, and FF D0+(r & 7) follows the last byte of every interval but the last -- written by the workgroup that owns that byte.  A thread finds
+// the interval of its first byte by one search in the entry's interval table (ends in bytes) and advances from there; an interval has at least one byte.
+// s_out: every byte leaves as at most four (itself, 00 behind an FF, a marker behind the last of an interval).
+__global__ void __launch_bounds__(EX_THREADS) k_export_stuff_rst(const JsExportRec* __restrict__ recs, const JsExportRstRec* __restrict__ rrecs, const uint32_t* __restrict__ chunk_base, uint32_t nrec,
+                                                                 const uint8_t* __restrict__ ustream, const uint64_t* __restrict__ chunk_off, const uint64_t* __restrict__ itab_all,
+                                                                 const uint8_t* __restrict__ hdrs, uint8_t* __restrict__ out, uint64_t* __restrict__ len)
+{
+    __shared__ uint32_t s_scan[EX_THREADS];
+    __shared__ uint8_t s_out[4u * JS_EXPORT_CHUNK];
+    __shared__ uint32_t s_r0, s_n;
+    const uint32_t t = threadIdx.x, chunk = blockIdx.x, k = ex_find(chunk_base, nrec, chunk);
+    const JsExportRec* rp = recs + k;
+    const uint32_t lc = chunk - chunk_base[k], nchunks = chunk_base[k + 1] - chunk_base[k], hdr_len = rp->hdr_len, ni = rrecs[k].ni;
+    const uint64_t* itab = itab_all + rrecs[k].itab_off;
+    const uint64_t nbytes = rp->bits >> 3, c0 = (uint64_t)lc * JS_EXPORT_CHUNK, at = c0 + t * 16u;
+    const uint32_t here = (uint32_t)min((uint64_t)JS_EXPORT_CHUNK, nbytes - c0);
+    uint8_t* file = out + rp->out_off;
+    ex_u32x4 v = { 0u, 0u, 0u, 0u }; uint32_t valid = 0, r = 0;
+    if (at < nbytes) {
+        v = *reinterpret_cast<const ex_u32x4*>(ustream + rp->u_off + at); valid = (uint32_t)min((uint64_t)16u, nbytes - at);
+        for (uint32_t top = ni - 1u; r < top; ) { const uint32_t mid = (r + top) >> 1; if (itab[mid] > at) top = mid; else r = mid + 1u; }      // the first interval that ends behind `at` (the last ends at nbytes)
+    }
+    if (t == 0) s_r0 = r;                                           // (the chunk's first byte exists: thread 0 searched)
+    uint32_t ff_here;
+    const uint32_t before = ex_scan(ex_ff16(v, valid), s_scan, &ff_here);
+    const uint32_t r0 = s_r0;
+    if (valid) {
+        uint32_t o = t * 16u + before + 2u * (r - r0); const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+        uint64_t end = itab[r];
+        #pragma unroll
+        for (uint32_t i = 0; i < 16u; i++) if (i < valid) {
+            const uint32_t b = (w[i >> 2] >> ((i & 3u) * 8u)) & 255u;
+            s_out[o++] = (uint8_t)b;
+            if (b == 255u) s_out[o++] = 0u;
+            if (at + i + 1u == end) {
+                if (r + 1u < ni) { s_out[o++] = 0xFFu; s_out[o++] = (uint8_t)(0xD0u + (r & 7u)); end = itab[r + 1u]; }
+                r++;
+            }
+        }
+        if (t * 16u + valid == here) s_n = o;                       // the thread with the chunk's last byte: everything the chunk writes
+    }
+    __syncthreads();
+    const uint64_t first = (uint64_t)hdr_len + c0 + chunk_off[chunk] + 2u * (uint64_t)r0;
+    uint8_t* dst = file + first;
+    const uint32_t n_out = s_n;
+    for (uint32_t i = t; i < n_out; i += EX_THREADS) dst[i] = s_out[i];
+    if (lc == 0u) { const uint8_t* h = hdrs + rp->hdr_off; for (uint32_t i = t; i < hdr_len; i += EX_THREADS) file[i] = h[i]; }
+    if (lc + 1u == nchunks && t == 0u) { dst[n_out] = 0xFFu; dst[n_out + 1u] = 0xD9u; len[k] = first + n_out + 2u; }
+}
+
 // ---- JSNOOP_HUFFMAN_OPTIMAL: the symbol counts of every entry, and T.81 Annex K.2 per entry and table (the definition: tests/export_opt_model.py) ----
 // k_export_symbols: k_export_measure's geometry, the same walk with a sink that counts: LDS atomics into a tile histogram laid out like the code tables, the words
 // that are not zero added to the entry's (indices masked in ex_walk: an uncodable entry stays inside its 544 words).
+template <bool RST>
 __global__ void __launch_bounds__(EX_THREADS) k_export_symbols(const int16_t* __restrict__ coef, const int16_t* __restrict__ dccum, const JsExportRec* __restrict__ recs,
-                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, JsExportOptStat* __restrict__ stats)
+                                                               const uint32_t* __restrict__ unit_base, uint32_t nrec, const uint32_t* __restrict__ tabs, JsExportOptStat* __restrict__ stats,
+                                                               const JsExportRstRec* __restrict__ rrecs /*RST only*/)
 {
     __shared__ ExShared s;
     __shared__ uint32_t s_hist[JS_EXPORT_TAB_WORDS];
@@ -329,7 +459,9 @@ __global__ void __launch_bounds__(EX_THREADS) k_export_symbols(const int16_t* __
     ex_stage(s, coef, *rp, t0, nb, tabs);
     if (t < nb) {
         uint32_t c;
-        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, t0 + t, &c);
+        uint32_t rb = 0u;
+        if constexpr (RST) rb = rrecs[k].ri_blocks;
+        const int32_t d = ex_dc_diff(dccum, rp, coef_off, bpm, t0 + t, rb, &c);
         const uint32_t tb = c ? 1u : 0u;
         ExSymbols sink{ s_hist + tb * 16u, s_hist + 32u + tb * 256u };
         ex_walk(s.rows + t * EX_ROW_HALVES, d, s.q[c], s.dc[tb], s.ac[tb], sink);
@@ -468,7 +600,7 @@ int js_launch_export_measure(hipStream_t st, const int16_t* coef, const int16_t*
                              const uint32_t* tabs, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
 {
     if (!nrec) return 0;
-    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, 0u, blk_bits, unit_bits, res);
+    if (total_units) hipLaunchKernelGGL(k_export_measure<false>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, 0u, blk_bits, unit_bits, res, (const JsExportRstRec*)nullptr, (JsRstSum*)nullptr);
     hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, unit_bits, unit_off, unit_base, ent_bits);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -477,9 +609,9 @@ int js_launch_export_measure_opt(hipStream_t st, const int16_t* coef, const int1
                                  uint32_t* hdr_len, uint16_t* blk_bits, uint32_t* unit_bits, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
 {
     if (!nrec) return 0;
-    if (total_units) hipLaunchKernelGGL(k_export_symbols, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, annex_tabs, stats);
+    if (total_units) hipLaunchKernelGGL(k_export_symbols<false>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, annex_tabs, stats, (const JsExportRstRec*)nullptr);
     hipLaunchKernelGGL(k_export_huff, dim3(nrec), dim3(EX_THREADS), 0, st, recs, orecs, unit_base, hdrs, stats, tabs, hdr_out, hdr_len);
-    if (total_units) hipLaunchKernelGGL(k_export_measure, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, JS_EXPORT_TAB_WORDS, blk_bits, unit_bits, res);
+    if (total_units) hipLaunchKernelGGL(k_export_measure<false>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, JS_EXPORT_TAB_WORDS, blk_bits, unit_bits, res, (const JsExportRstRec*)nullptr, (JsRstSum*)nullptr);
     hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, unit_bits, unit_off, unit_base, ent_bits);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -488,7 +620,7 @@ static int ex_launch_write(hipStream_t st, const int16_t* coef, const int16_t* d
                            uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
 {
     if (!nrec || !total_units || !total_chunks) return 0;
-    hipLaunchKernelGGL(k_export_bits, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, tab_stride, blk_bits, unit_off, ustream);
+    hipLaunchKernelGGL(k_export_bits<false>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, tab_stride, blk_bits, unit_off, ustream, (const JsExportRstRec*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_ff);
     hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, chunk_ff, chunk_off, chunk_base, ent_ff);
     hipLaunchKernelGGL(k_export_stuff, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, ustream, chunk_off, hdrs, out, len);
@@ -505,4 +637,31 @@ int js_launch_export_write_opt(hipStream_t st, const int16_t* coef, const int16_
                                uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
 {
     return ex_launch_write(st, coef, dccum, recs, unit_base, chunk_base, nrec, total_units, total_chunks, tabs, JS_EXPORT_TAB_WORDS, blk_bits, unit_off, ustream, chunk_ff, chunk_off, ent_ff, hdrs, out, len);
+}
+
+// ---- jsnoop_batch_export_jpeg_rst: the two phases with the restart forms of the kernels.  orecs == NULL: the Annex K tables (annex_tabs: one set), else every entry's own.
+int js_launch_export_measure_rst(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportOptRec* orecs, const JsExportRstRec* rrecs,
+                                 const uint32_t* unit_base, uint32_t nrec, uint32_t total_units, const uint32_t* annex_tabs, const uint8_t* hdrs, JsExportOptStat* stats, uint32_t* tabs,
+                                 uint8_t* hdr_out, uint32_t* hdr_len, uint16_t* blk_bits, JsRstSum* unit_sum, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits)
+{
+    if (!nrec) return 0;
+    if (orecs) {
+        if (total_units) hipLaunchKernelGGL(k_export_symbols<true>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, annex_tabs, stats, rrecs);
+        hipLaunchKernelGGL(k_export_huff, dim3(nrec), dim3(EX_THREADS), 0, st, recs, orecs, unit_base, hdrs, stats, tabs, hdr_out, hdr_len);
+    }
+    if (total_units) hipLaunchKernelGGL(k_export_measure<true>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, orecs ? (const uint32_t*)tabs : annex_tabs,
+                                        orecs ? JS_EXPORT_TAB_WORDS : 0u, blk_bits, (uint32_t*)nullptr, res, rrecs, unit_sum);
+    hipLaunchKernelGGL(k_export_rst_scan, dim3(nrec), dim3(EX_THREADS), 0, st, (const JsRstSum*)unit_sum, unit_off, unit_base, ent_bits);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int js_launch_export_write_rst(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportRstRec* rrecs, const uint32_t* unit_base,
+                               const uint32_t* chunk_base, uint32_t nrec, uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, uint32_t tab_stride, const uint16_t* blk_bits,
+                               const uint64_t* unit_off, uint64_t* itab, uint8_t* ustream, uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len)
+{
+    if (!nrec || !total_units || !total_chunks) return 0;
+    hipLaunchKernelGGL(k_export_bits<true>, dim3(total_units), dim3(EX_THREADS), 0, st, coef, dccum, recs, unit_base, nrec, tabs, tab_stride, blk_bits, unit_off, ustream, rrecs, itab);
+    hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, (const uint8_t*)ustream, chunk_ff);
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, (const uint32_t*)chunk_ff, chunk_off, chunk_base, ent_ff);
+    hipLaunchKernelGGL(k_export_stuff_rst, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, rrecs, chunk_base, nrec, (const uint8_t*)ustream, (const uint64_t*)chunk_off, (const uint64_t*)itab, hdrs, out, len);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }

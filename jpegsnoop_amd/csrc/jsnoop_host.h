@@ -142,9 +142,12 @@ struct JsnoopBatch {
     // tables and its header on the device in front of the first wait (d_export_opt: JsExportOptStat, code tables and headers per entry; export_opt says the last
     // export left them there for export_tables, one staged copy on demand)
     int  export_jpeg_coded(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const int* images, int n);
+    // jsnoop_batch_export_jpeg_rst: export_jpeg_coded with a restart interval per entry (jsnoop_export_rst_check.h).  A call in which no entry has one runs
+    // export_jpeg_coded's launches; otherwise the restart forms of the kernels run for the whole call (an entry without an interval is one interval to them)
+    int  export_jpeg_rst(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const int* images, int n);
     int  export_tables(int k, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq);
     uint8_t* d_export_opt = nullptr; size_t d_export_opt_cap = 0; bool export_opt = false;
-    struct JsExportEntry { uint64_t off, len; int result; uint32_t detail; int image; };   // entry k of the last export: its file at d_export_out + off
+    struct JsExportEntry { uint64_t off, len; int result; uint32_t detail; int image; uint32_t ri = 0; uint64_t intervals = 0; };   // entry k of the last export: its file at d_export_out + off
     std::vector<JsExportEntry> exports;
     uint8_t* d_export_tmp = nullptr; size_t d_export_tmp_cap = 0; // scratch of the first phase: result words, bit lengths per block / tile / entry
     uint8_t* d_export_u = nullptr; size_t d_export_u_cap = 0;     // the chunk tables and the un-stuffed streams of the second phase

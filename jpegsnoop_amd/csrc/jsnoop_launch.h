@@ -134,6 +134,17 @@ int  js_launch_export_measure_opt(hipStream_t st, const int16_t* coef, const int
 int  js_launch_export_write_opt(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const uint32_t* unit_base, const uint32_t* chunk_base, uint32_t nrec,
                                 uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, const uint16_t* blk_bits, const uint64_t* unit_off, uint8_t* ustream,
                                 uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
+// jsnoop_batch_export_jpeg_rst (restart intervals): both phases with the restart forms of the kernels -- k_export_symbols / k_export_measure / k_export_bits with the DC
+// predecessor reset at every interval start, k_export_rst_scan (positions from run summaries: an interval starts on a byte), k_export_stuff_rst (markers between the
+// intervals).  rrecs: the side records; unit_sum: one JsRstSum per unit; itab: the call's interval tables (filled by k_export_bits, read by k_export_stuff_rst).
+// orecs == NULL: the Annex K tables (annex_tabs), else every entry's own, built as in js_launch_export_measure_opt.  tabs / tab_stride of the second phase: the one set
+// and 0, or the entries' own and JS_EXPORT_TAB_WORDS.
+int  js_launch_export_measure_rst(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportOptRec* orecs, const JsExportRstRec* rrecs,
+                                  const uint32_t* unit_base, uint32_t nrec, uint32_t total_units, const uint32_t* annex_tabs, const uint8_t* hdrs, JsExportOptStat* stats, uint32_t* tabs,
+                                  uint8_t* hdr_out, uint32_t* hdr_len, uint16_t* blk_bits, JsRstSum* unit_sum, uint64_t* unit_off, uint32_t* res, uint64_t* ent_bits);
+int  js_launch_export_write_rst(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportRstRec* rrecs, const uint32_t* unit_base,
+                                const uint32_t* chunk_base, uint32_t nrec, uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, uint32_t tab_stride, const uint16_t* blk_bits,
+                                const uint64_t* unit_off, uint64_t* itab, uint8_t* ustream, uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
 // jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
 // head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
 // the two totals as 64-bit words).  0, -1 on a launch error.

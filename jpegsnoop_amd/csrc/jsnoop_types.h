@@ -202,6 +202,14 @@ struct JsExportRec { uint64_t coef_off, blk_base, bits, u_off, out_off, out_cap;
 struct JsExportOptRec { uint32_t pre_len, sos_off, sos_len, nslots; };
 struct JsExportOptSlot { uint32_t nsym; uint8_t counts[16]; uint8_t syms[256]; };
 struct JsExportOptStat { uint32_t freq[544]; JsExportOptSlot slot[4]; };
+// jsnoop_batch_export_jpeg_rst (restart intervals in the written files; arithmetic: jsnoop_export_rst_check.h): a side record per entry beside JsExportRec.
+// ri_blocks: the entry's restart interval in BLOCKS (Ri x blocks per MCU; 0: the entry is written without restart markers, one interval), ni: its intervals,
+// itab_off: where its interval table lies in the call's table (one uint64 per interval: the interval's end in bytes of the un-stuffed stream, in which every
+// interval is padded to a whole byte and no marker stands).
+struct JsExportRstRec { uint64_t itab_off; uint32_t ri_blocks, ni; };
+// The summary of a run of blocks under that rule: has -- an interval ends inside the run; head -- the bits in front of the first such end (all bits where has
+// is 0); mid -- whole bytes between the first and the last end; tail -- the bits behind the last end.  js_rst_combine (jsnoop_export_rst_check.h) is associative.
+struct JsRstSum { uint32_t has, head, mid, tail; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

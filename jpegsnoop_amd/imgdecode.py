@@ -83,10 +83,13 @@ class CimgDecode:
     def ExportTiff(self, path: str, nMode: int = 0) -> bool:
         return self._lib.jsnoop_export_tiff(self._h, path.encode(), nMode) == 0
 
-    def export_jpeg(self, path: str, huffman: str = "annex_k") -> bool:
+    def export_jpeg(self, path: str, huffman: str = "annex_k", restart=0) -> bool:
         """The decoded image written back as a baseline JPEG file (jsnoop_export_jpeg): the coefficients the decoder holds, entropy-coded on the
         device.  False, and no file, where the image cannot be exported (capi.last_error() has the reason).  huffman="optimal": with the image's own
-        Huffman tables (jsnoop_export_jpeg_coded)."""
+        Huffman tables (jsnoop_export_jpeg_coded).  restart: as in JpegBatch.export_jpeg (jsnoop_export_jpeg_rst)."""
+        rst = capi.export_restart(self._lib, restart)
+        if rst.mode != capi.RESTART_NONE:
+            return self._lib.jsnoop_export_jpeg_rst(self._h, path.encode(), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst)) == 0
         if huffman == "annex_k":
             return self._lib.jsnoop_export_jpeg(self._h, path.encode()) == 0
         return self._lib.jsnoop_export_jpeg_coded(self._h, path.encode(), C.byref(capi.export_coding(self._lib, huffman))) == 0
@@ -835,18 +838,22 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_log(self._h, i, int(histo_en), int(stat_clip_en), int(quiet), cb, None), "batch_log")
         return out
 
-    def _export(self, images, jfif, what, huffman="annex_k"):
+    def _export(self, images, jfif, what, huffman="annex_k", restart=0):
         n_all = len(self)
         idx = list(range(n_all)) if images is None else [int(i) for i in images]
         for i in idx:
             if not 0 <= i < n_all:
                 raise IndexError(f"{what}: image index {i} out of range, the batch holds {n_all}")
+        rst = capi.export_restart(self._lib, restart)                 # (refuses what is no restart value before anything is done)
         spec = capi.ExportSpec()
         self._lib.jsnoop_export_spec_defaults(C.byref(spec))
         spec.jfif = 1 if jfif else 0
         self.sync()
         ind = (C.c_int * max(len(idx), 1))(*idx)
-        if huffman == "annex_k":
+        if rst.mode != capi.RESTART_NONE:
+            self._chk(self._lib.jsnoop_batch_export_jpeg_rst(self._h, C.byref(spec), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst), ind, len(idx)),
+                      "batch_export_jpeg_rst")
+        elif huffman == "annex_k":
             self._chk(self._lib.jsnoop_batch_export_jpeg(self._h, C.byref(spec), ind, len(idx)), "batch_export_jpeg")
         else:
             self._chk(self._lib.jsnoop_batch_export_jpeg_coded(self._h, C.byref(spec), C.byref(capi.export_coding(self._lib, huffman)), ind, len(idx)), "batch_export_jpeg_coded")
@@ -865,6 +872,13 @@ class JpegBatch:
             out.append(dict(slot=slot, freq=list(freq), counts=list(counts), symbols=list(syms[:n.value])))
         return out
 
+    def export_restart(self, k):
+        """Entry k of the last export: (Ri, intervals) -- the restart interval in MCUs it was written with (0: none) and the number of intervals of its file
+        (0 where no file was written) (jsnoop_batch_export_restart)."""
+        ri, n = C.c_uint32(), C.c_uint64()
+        self._chk(self._lib.jsnoop_batch_export_restart(self._h, int(k), C.byref(ri), C.byref(n)), "batch_export_restart")
+        return int(ri.value), int(n.value)
+
     def export_results(self):
         """The entries of the last export_jpeg / export_jpeg_to_torch, in the order of its list: dicts with image, result (capi.EXPORT_OK / _INEXACT /
         _UNCODABLE / _UNSUPPORTED), detail (the lowest offending block of the image, decode order; 0 where the result has none), len (0 unless OK)
@@ -876,15 +890,18 @@ class JpegBatch:
             out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
         return out
 
-    def export_jpeg(self, images=None, jfif=True, huffman="annex_k"):
+    def export_jpeg(self, images=None, jfif=True, huffman="annex_k", restart=0):
         """What the batch holds for the listed images (None = all; any order, repeats allowed) written back as baseline JPEG files, entropy-coded on
         the device by ONE jsnoop_batch_export_jpeg: a list with the file's bytes per entry, None where the image could not be exported
         (export_results() says why).  An exported file decodes to the same coefficients; where the source was a clean file, to the same pixels.
         jfif=False leaves the APP0 segment out.  Calls sync() first (a damaged file is exported as repaired); behind a DC-only fast-form decode the
         batch is decoded once more in the generic form.  huffman="optimal": every file with its own Huffman tables, built on the device from the
-        image's symbol counts (export_tables(k) returns them); "annex_k" (the default): the tables of T.81 Annex K."""
+        image's symbol counts (export_tables(k) returns them); "annex_k" (the default): the tables of T.81 Annex K.  restart: 0 (the default) writes no
+        restart markers; an int the interval in MCUs; ("rows", n) n MCU rows of each image; "source" the interval each image was decoded with (none where it
+        had none).  With an interval the files carry DRI and FF D0..D7 between the intervals (jsnoop_batch_export_jpeg_rst; export_restart(k) says what entry
+        k got); an image whose interval comes out above 65535 is not exported (capi.EXPORT_UNSUPPORTED)."""
         files = []
-        for k, e in enumerate(self._export(images, jfif, "export_jpeg", huffman)):
+        for k, e in enumerate(self._export(images, jfif, "export_jpeg", huffman, restart)):
             if not e["len"]:
                 files.append(None); continue
             buf = (C.c_uint8 * e["len"])()
@@ -894,12 +911,12 @@ class JpegBatch:
             files.append(bytes(buf))
         return files
 
-    def export_jpeg_to_torch(self, images=None, jfif=True, huffman="annex_k"):
+    def export_jpeg_to_torch(self, images=None, jfif=True, huffman="annex_k", restart=0):
         """export_jpeg, but the files stay on the device: a list with one uint8 tensor per entry (None where the image could not be exported), copied
         out of the batch's memory by jsnoop_batch_export_copy -- they outlive the next export."""
         import torch
         dev = torch.device("cuda", self.device())
-        res = self._export(images, jfif, "export_jpeg_to_torch", huffman)
+        res = self._export(images, jfif, "export_jpeg_to_torch", huffman, restart)
         sizes = [-(-e["len"] // 16) * 16 for e in res]
         flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
         cur = torch.cuda.current_stream(dev)
