@@ -692,6 +692,38 @@ void         jsnoop_export_restart_defaults(JsnoopExportRestart* out);          
 int          jsnoop_batch_export_jpeg_rst(JsnoopBatch*, const JsnoopExportSpec*, const JsnoopExportCoding*, const JsnoopExportRestart*, const int* images, int n);
 int          jsnoop_batch_export_restart(const JsnoopBatch*, int k, uint32_t* ri, uint64_t* intervals);   /* what entry k of the last export was written with */
 int          jsnoop_export_jpeg_rst(JsnoopDecoder*, const char* path, const JsnoopExportCoding*, const JsnoopExportRestart*);
+/* Progressive (SOF2) files.  jsnoop_batch_export_jpeg_prog is jsnoop_batch_export_jpeg_rst with a fourth spec: mode JSNOOP_PROGRESSIVE_OFF is that call byte for
+ * byte and launch for launch; DEFAULT writes the built-in scan script, SCRIPT the caller's (tests/export_prog_model.py is the definition, byte for byte; DESIGN.md
+ * section 4.17 has the contract, the rules of a script and the default scripts).  A script is a list of scans (components as a bit mask, Ss, Se, Ah, Al): DC scans
+ * (Ss = Se = 0) with successive approximation, AC scans of one component by spectral selection (Ah = Al = 0).  AC successive approximation is not written: a
+ * script that asks for it, or breaks any other rule, is refused with -1 and a text before anything is launched or cleared (the previous export stays valid), and
+ * so are an unknown mode, SCRIPT with NULL scans or nscans of 0 or above JSNOOP_EXPORT_MAX_SCANS, OFF / DEFAULT with a script, non-zero reserved fields, comps
+ * bits 3..7 and a longer struct.  Every scan carries its own optimal Huffman tables, built on the device from the scan's symbol counts: coding.huffman is
+ * validated as before, but BOTH values write own tables in a progressive mode, because Annex K has no codes for the end-of-band runs EOBn.
+ * The restart spec counts in every scan's own units: MCUS n is Ri = n in every scan, ROWS r is Ri = r x the scan's units per row (mcu_xmax of an interleaved
+ * scan, the width in blocks of the component's coded part in a one-component scan), SOURCE the image's recorded interval as MCUS.  DRI stands in front of the SOS
+ * of every scan whose Ri differs from the one in force.  An entry whose component count differs from the script's, with a precision other than 8, with an Ri above
+ * 65535 in some scan, or with 2^26 blocks or more is JSNOOP_EXPORT_UNSUPPORTED (host arithmetic; the other entries are written).  DC levels are the ABSOLUTE
+ * values (int16)dccum / q[0] (a remainder is INEXACT), coded as differences of their point transforms inside every restart interval (beyond +-2047: UNCODABLE).
+ * jsnoop_batch_export_file, _read_export, _export_copy, _export_count, ownership and invalidation are jsnoop_batch_export_jpeg's; jsnoop_batch_export_restart
+ * returns the FIRST scan's values on a progressive entry; jsnoop_batch_export_tables refuses one (jsnoop_batch_export_scan_tables is its call).
+ * jsnoop_batch_export_scan_count: the scans entry k was written with (0 for a baseline or absent file).  jsnoop_batch_export_scan_info: scan `scan` of entry k --
+ * the script's scan, its Ri in its own units, its intervals, where its SOS marker stands in the file and the bytes of its entropy-coded data (stuffing and RSTn
+ * included); any output pointer may be NULL.  jsnoop_batch_export_scan_tables: table `slot` of that scan (a DC first scan: one per scan component, in the scan's
+ * order; an AC scan: slot 0; a refinement scan has none) as jsnoop_batch_export_tables returns a table.  jsnoop_export_jpeg_prog: jsnoop_export_jpeg_rst with a
+ * progressive spec.  The call waits for the device twice, as every export does. */
+#define JSNOOP_PROGRESSIVE_OFF     0
+#define JSNOOP_PROGRESSIVE_DEFAULT 1
+#define JSNOOP_PROGRESSIVE_SCRIPT  2
+#define JSNOOP_EXPORT_MAX_SCANS    256u
+typedef struct JsnoopExportScan { uint8_t comps /* bit c = component c */, ss, se, ah, al, reserved[3]; } JsnoopExportScan;
+typedef struct JsnoopExportProgressive { uint32_t struct_size; int32_t mode; uint32_t nscans; uint32_t reserved; const JsnoopExportScan* scans; } JsnoopExportProgressive;
+void         jsnoop_export_progressive_defaults(JsnoopExportProgressive* out);                 /* OFF; NULL tolerated */
+int          jsnoop_batch_export_jpeg_prog(JsnoopBatch*, const JsnoopExportSpec*, const JsnoopExportCoding*, const JsnoopExportRestart*, const JsnoopExportProgressive*, const int* images, int n);
+int          jsnoop_batch_export_scan_count(const JsnoopBatch*, int k);
+int          jsnoop_batch_export_scan_info(const JsnoopBatch*, int k, int scan, JsnoopExportScan* sc, uint32_t* ri, uint64_t* intervals, uint64_t* sos_offset, uint64_t* data_bytes);
+int          jsnoop_batch_export_scan_tables(JsnoopBatch*, int k, int scan, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256]);
+int          jsnoop_export_jpeg_prog(JsnoopDecoder*, const char* path, const JsnoopExportCoding*, const JsnoopExportRestart*, const JsnoopExportProgressive*);
 
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and

@@ -182,6 +182,50 @@ def export_restart(lib, restart):
     return r
 
 
+PROGRESSIVE_OFF, PROGRESSIVE_DEFAULT, PROGRESSIVE_SCRIPT = 0, 1, 2
+EXPORT_MAX_SCANS = 256  # JSNOOP_EXPORT_MAX_SCANS of include/jsnoop_gpu.h
+
+
+class ExportScan(C.Structure):
+    """JsnoopExportScan of include/jsnoop_gpu.h: one scan of a progressive script (comps: bit c = component c)."""
+    _fields_ = [("comps", C.c_uint8), ("ss", C.c_uint8), ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class ExportProgressive(C.Structure):
+    """JsnoopExportProgressive of include/jsnoop_gpu.h: the scan script jsnoop_batch_export_jpeg_prog writes progressive files along."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("nscans", C.c_uint32), ("reserved", C.c_uint32), ("scans", C.POINTER(ExportScan))]
+
+
+def export_progressive(lib, progressive):
+    """The JsnoopExportProgressive of progressive = False (baseline) | True (the built-in script) | a list of scans (components, ss, se, ah, al),
+    components an iterable of indices or one index.  The scans are handed to the library as given: it refuses a script that breaks a rule.  The struct
+    keeps the scan array alive (._scans)."""
+    p = ExportProgressive()
+    lib.jsnoop_export_progressive_defaults(C.byref(p))
+    if progressive is False or progressive is None:
+        return p
+    if progressive is True:
+        p.mode = PROGRESSIVE_DEFAULT
+        return p
+    try:
+        scans = [tuple(s) for s in progressive]
+        arr = (ExportScan * max(len(scans), 1))()
+        for i, (comps, ss, se, ah, al) in enumerate(scans):
+            mask = 0
+            for c in ([comps] if isinstance(comps, int) else comps):
+                if not 0 <= int(c) < 8:
+                    raise ValueError
+                mask |= 1 << int(c)
+            for v in (ss, se, ah, al):                                    # (a c_uint8 field would take 319 as 63 without a word)
+                if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+                    raise ValueError
+            arr[i].comps = mask; arr[i].ss = ss; arr[i].se = se; arr[i].ah = ah; arr[i].al = al
+    except (TypeError, ValueError):
+        raise ValueError("progressive must be False, True or a list of scans (components, ss, se, ah, al) with values 0 .. 255, not %r" % (progressive,)) from None
+    p.mode = PROGRESSIVE_SCRIPT; p.nscans = len(scans); p.scans = C.cast(arr, C.POINTER(ExportScan)); p._scans = arr
+    return p
+
+
 CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
 CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
 CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
@@ -361,6 +405,12 @@ SIGNATURES = {
     "jsnoop_batch_export_jpeg_rst": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), C.POINTER(ExportRestart), _PI, _i]),
     "jsnoop_batch_export_restart": (_i, [_p, _i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "jsnoop_export_jpeg_rst": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding), C.POINTER(ExportRestart)]),
+    "jsnoop_export_progressive_defaults": (None, [C.POINTER(ExportProgressive)]),
+    "jsnoop_batch_export_jpeg_prog": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), C.POINTER(ExportRestart), C.POINTER(ExportProgressive), _PI, _i]),
+    "jsnoop_batch_export_scan_count": (_i, [_p, _i]),
+    "jsnoop_batch_export_scan_info": (_i, [_p, _i, _i, C.POINTER(ExportScan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jsnoop_batch_export_scan_tables": (_i, [_p, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "jsnoop_export_jpeg_prog": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding), C.POINTER(ExportRestart), C.POINTER(ExportProgressive)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

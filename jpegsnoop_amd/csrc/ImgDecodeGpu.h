@@ -138,6 +138,12 @@ public:
     { JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = bOptimal ? JSNOOP_HUFFMAN_OPTIMAL : JSNOOP_HUFFMAN_ANNEX_K;
       JsnoopExportRestart rst; jsnoop_export_restart_defaults(&rst); rst.mode = nMode; rst.interval = nInterval;
       return jsnoop_export_jpeg_rst(m_h, strFnameOut.c_str(), &coding, &rst) == 0; }
+    // ... as a progressive file (jsnoop_export_jpeg_prog): scans empty: the built-in script, else the caller's (DESIGN.md 4.17 has the rules)
+    bool ExportJpegProgressive(const std::string& strFnameOut, int nMode, unsigned nInterval, const std::vector<JsnoopExportScan>& scans = {})
+    { JsnoopExportRestart rst; jsnoop_export_restart_defaults(&rst); rst.mode = nMode; rst.interval = nInterval;
+      JsnoopExportProgressive prog; jsnoop_export_progressive_defaults(&prog); prog.mode = scans.empty() ? JSNOOP_PROGRESSIVE_DEFAULT : JSNOOP_PROGRESSIVE_SCRIPT;
+      prog.nscans = (uint32_t)scans.size(); prog.scans = scans.empty() ? nullptr : scans.data();
+      return jsnoop_export_jpeg_prog(m_h, strFnameOut.c_str(), nullptr, &rst, &prog) == 0; }
     // hover helpers next to LookupFilePosMcu (source/JPEGsnoopViewImg.cpp:294-334); CPoint is a pair of unsigned here
     void PixelToMcu(unsigned nPixX, unsigned nPixY, unsigned& nMcuX, unsigned& nMcuY) { jsnoop_pixel_to_mcu(m_h, nPixX, nPixY, &nMcuX, &nMcuY); }               // :5056
     void PixelToBlk(unsigned nPixX, unsigned nPixY, unsigned& nBlkX, unsigned& nBlkY) { jsnoop_pixel_to_blk(m_h, nPixX, nPixY, &nBlkX, &nBlkY); }               // :5071
@@ -289,6 +295,18 @@ public:
       const int n = files.empty() ? jsnoop_batch_count(m_b) : (int)files.size();
       return jsnoop_batch_export_jpeg_rst(m_b, &spec, &coding, &rst, files.empty() ? nullptr : files.data(), n) == 0; }
     bool     BatchExportRestart(int k, uint32_t& nRi, uint64_t& nIntervals) const { return jsnoop_batch_export_restart(m_b, k, &nRi, &nIntervals) == 0; }
+    // BatchExportJpegRestart as progressive files (jsnoop_batch_export_jpeg_prog): scans empty: the built-in script, else the caller's; every scan carries its own
+    // optimal tables.  BatchExportScanCount / BatchExportScanInfo: the scans entry k was written with
+    bool     BatchExportJpegProgressive(const std::vector<int>& files, bool bJfif, int nMode, unsigned nInterval, const std::vector<JsnoopExportScan>& scans = {})
+    { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;
+      JsnoopExportRestart rst; jsnoop_export_restart_defaults(&rst); rst.mode = nMode; rst.interval = nInterval;
+      JsnoopExportProgressive prog; jsnoop_export_progressive_defaults(&prog); prog.mode = scans.empty() ? JSNOOP_PROGRESSIVE_DEFAULT : JSNOOP_PROGRESSIVE_SCRIPT;
+      prog.nscans = (uint32_t)scans.size(); prog.scans = scans.empty() ? nullptr : scans.data();
+      const int n = files.empty() ? jsnoop_batch_count(m_b) : (int)files.size();
+      return jsnoop_batch_export_jpeg_prog(m_b, &spec, nullptr, &rst, &prog, files.empty() ? nullptr : files.data(), n) == 0; }
+    int      BatchExportScanCount(int k) const { return jsnoop_batch_export_scan_count(m_b, k); }
+    bool     BatchExportScanInfo(int k, int nScan, JsnoopExportScan& scan, uint32_t& nRi, uint64_t& nIntervals, uint64_t& nSosOffset, uint64_t& nDataBytes) const
+    { return jsnoop_batch_export_scan_info(m_b, k, nScan, &scan, &nRi, &nIntervals, &nSosOffset, &nDataBytes) == 0; }
     bool     BatchExportTables(int k, int nSlot, uint8_t anCounts[16], uint8_t anSymbols[256], uint32_t& nSymbols, uint32_t anFreq[256])
     { return jsnoop_batch_export_tables(m_b, k, nSlot, anCounts, anSymbols, &nSymbols, anFreq) == 0; }
     int      BatchExportCount() const { return jsnoop_batch_export_count(m_b); }

@@ -3,7 +3,7 @@
 #include <stdio.h>
 #include "jsnoop_host.h"
 #include "jsnoop_launch.h"
-#include "jsnoop_export_rst_check.h"
+#include "jsnoop_export_prog_check.h"
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     js_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
@@ -53,7 +53,7 @@ int JsnoopBatch::export_jpeg_rst(const JsnoopExportSpec* spec_in, const JsnoopEx
     if (js_export_import_spec(spec_in, &spec)) return -1;
     if (n < 0) { js_set_error("export_jpeg: n = %d", n); return -1; }
     if (!images && (size_t)n > imgs.size()) { js_set_error("export_jpeg: n = %d without a list, the batch holds %zu", n, imgs.size()); return -1; }
-    exports.clear(); export_opt = false;
+    exports.clear(); export_opt = false; export_prog = false;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(device));
     bool rst = false;                                            // some listed entry is written with a restart interval (or refused for one too large)
@@ -158,6 +158,7 @@ int JsnoopBatch::export_jpeg_rst(const JsnoopExportSpec* spec_in, const JsnoopEx
 int JsnoopBatch::export_tables(int k, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq)
 {
     if (k < 0 || (size_t)k >= exports.size()) { js_set_error("export_tables: entry %d out of range, the last export holds %zu", k, exports.size()); return -1; }
+    if (export_prog) { js_set_error("export_tables: the last export wrote progressive files, whose tables belong to scans: jsnoop_batch_export_scan_tables returns them"); return -1; }
     if (!export_opt || !d_export_opt) { js_set_error("export_tables: the last export wrote the Annex K tables (huffman = 0): it built none"); return -1; }
     const JsExportEntry& e = exports[(size_t)k];
     if (e.result != JSNOOP_EXPORT_OK) { js_set_error("export_tables: entry %d was not exported (result %d): it has no tables", k, e.result); return -1; }
@@ -175,6 +176,146 @@ int JsnoopBatch::export_tables(int k, int slot, uint8_t* counts, uint8_t* symbol
     if (freq) {
         memset(freq, 0, 256 * 4);
         if (slot & 1) memcpy(freq, st[0].freq + 32 + (slot >> 1) * 256, 256 * 4); else memcpy(freq, st[0].freq + (slot >> 1) * 16, 16 * 4);
+    }
+    return 0;
+}
+
+// Progressive files (jsnoop_export_prog_check.h has the arithmetic, DESIGN.md 4.17 the contract).  The same two phases and two waits with a record per (entry, scan):
+//   1. k_prog_classify, k_prog_runs, k_prog_symbols, k_prog_huff, k_prog_measure, k_export_rst_scan; result words, the scans' stream lengths and header-piece
+//      lengths come back (wait 1): the host sizes the un-stuffed streams and the files.
+//   2. the streams zeroed, k_prog_bits, k_prog_ffcount, k_export_scan, k_prog_place, k_prog_stuff; the file lengths, the scans' places and FF counts come back (wait 2).
+int JsnoopBatch::export_jpeg_prog(const JsnoopExportSpec* spec_in, const JsnoopExportCoding* coding_in, const JsnoopExportRestart* restart_in, const JsnoopExportProgressive* prog_in,
+                                  const int* images, int n)
+{
+    JsnoopExportProgressive prog;
+    if (js_export_import_progressive(prog_in, &prog)) return -1;
+    if (prog.mode == JSNOOP_PROGRESSIVE_OFF) return export_jpeg_rst(spec_in, coding_in, restart_in, images, n);
+    JsnoopExportCoding coding;
+    if (js_export_import_coding(coding_in, &coding)) return -1;      // (validated; both values write the scans' own tables)
+    JsnoopExportRestart restart;
+    if (js_export_import_restart(restart_in, &restart)) return -1;
+    std::vector<JsnoopExportScan> script3, script1;
+    if (prog.mode == JSNOOP_PROGRESSIVE_DEFAULT) {
+        script3.resize(6); script1.resize(4);
+        js_export_prog_default(3u, script3.data()); js_export_prog_default(1u, script1.data());
+    } else {
+        uint32_t nc = 0;
+        if (js_export_prog_validate(prog.scans, prog.nscans, &nc)) return -1;
+        (nc == 1u ? script1 : script3).assign(prog.scans, prog.scans + prog.nscans);
+    }
+    if (!uploaded || last_form == 0 || !dev.coef || !dev.dccum) { js_set_error("export_jpeg: the batch has not been decoded"); return -1; }
+    JsnoopExportSpec spec;
+    if (js_export_import_spec(spec_in, &spec)) return -1;
+    if (n < 0) { js_set_error("export_jpeg: n = %d", n); return -1; }
+    if (!images && (size_t)n > imgs.size()) { js_set_error("export_jpeg: n = %d without a list, the batch holds %zu", n, imgs.size()); return -1; }
+    const JsnoopExportScan* s3 = script3.empty() ? nullptr : script3.data(); const JsnoopExportScan* s1 = script1.empty() ? nullptr : script1.data();
+    const uint32_t n3 = (uint32_t)script3.size(), n1 = (uint32_t)script1.size();
+    std::vector<uint8_t> refused((size_t)n), unsupported((size_t)n);
+    size_t nrec = 0;
+    if (js_export_prog_count(imgs.data(), imgs.size(), images, n, restart, s3, n3, s1, n1, refused.data(), &nrec)) return -1;      // (an index out of range too leaves the previous export)
+    exports.clear(); export_opt = false; export_prog = false; export_scans.clear(); export_scan_base.clear();
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(device));
+    const JsExportProgBlock blk = js_export_prog_block((size_t)n, nrec);
+    if (pack_block(blk.b.total)) return -1;
+    JsExportRec* recs = reinterpret_cast<JsExportRec*>(h_pack + blk.b.recs);
+    uint32_t* rec_base = reinterpret_cast<uint32_t*>(h_pack + blk.b.unit_base);
+    JsExportScanRec* srecs = reinterpret_cast<JsExportScanRec*>(h_pack + blk.srecs);
+    uint32_t* tile_base = reinterpret_cast<uint32_t*>(h_pack + blk.tile_base); uint32_t* chunk_base = reinterpret_cast<uint32_t*>(h_pack + blk.chunk_base);
+    uint64_t blocks = 0, units = 0, intervals = 0;
+    if (js_export_plan(imgs.data(), imgs.size(), spec, images, n, js_export_q, this, recs, rec_base, h_pack + blk.b.hdrs, unsupported.data(), &blocks)) return -1;
+    for (int k = 0; k < n; k++) unsupported[(size_t)k] |= refused[(size_t)k];
+    if (js_export_prog_plan(imgs.data(), images, n, restart, s3, n3, s1, n1, recs, unsupported.data(), h_pack + blk.b.hdrs, (uint32_t)(blk.posts - blk.b.hdrs), srecs, rec_base, tile_base,
+                            &units, &intervals)) return -1;
+    if (rec_base[n] != nrec) { js_set_error("export_jpeg: %u scan records planned, %zu counted", rec_base[n], nrec); return -1; }
+    memset(chunk_base, 0, (nrec + 1) * 4);
+    if (ensure_generic()) return -1;
+    const uint32_t tiles = tile_base[nrec];
+    const JsExportProgScratch sc = js_export_prog_scratch((size_t)n, nrec, tiles, units, intervals);
+    const JsExportProgKeep keep = js_export_prog_keep(nrec);
+    if (js_export_grow(&d_export_tmp, &d_export_tmp_cap, sc.total) || js_export_grow(&d_export_opt, &d_export_opt_cap, keep.total)) return -1;
+    if (pack_send(blk.b.total)) return -1;
+    HIP_TRY(hipMemsetAsync(d_export_tmp + sc.res, 0, (size_t)n * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_export_tmp + sc.res + (size_t)n * 4, 0xFF, (size_t)n * 8, stream));
+    HIP_TRY(hipMemsetAsync(d_export_tmp + sc.rec_bits, 0, sc.back2 - sc.rec_bits, stream));
+    if (nrec) HIP_TRY(hipMemsetAsync(d_export_opt + keep.stats, 0, nrec * sizeof(JsExportScanStat), stream));      // (a call in which every entry is unsupported has no record)
+    const JsExportRec* d_recs = reinterpret_cast<const JsExportRec*>(d_pack + blk.b.recs); const JsExportScanRec* d_srecs = reinterpret_cast<const JsExportScanRec*>(d_pack + blk.srecs);
+    const uint32_t* d_tile_base = reinterpret_cast<const uint32_t*>(d_pack + blk.tile_base);
+    uint32_t* d_tabs = reinterpret_cast<uint32_t*>(d_export_opt + keep.tabs); uint32_t* d_hdr_len = reinterpret_cast<uint32_t*>(d_export_tmp + sc.hdr_len);
+    uint16_t* d_eob = reinterpret_cast<uint16_t*>(d_export_tmp + sc.eob); uint16_t* d_blk_bits = reinterpret_cast<uint16_t*>(d_export_tmp + sc.blk_bits);
+    uint64_t* d_tile_off = reinterpret_cast<uint64_t*>(d_export_tmp + sc.tile_off);
+    if (js_launch_export_prog_measure(stream, dev.coef, dev.dccum, d_recs, d_srecs, d_tile_base, (uint32_t)n, (uint32_t)nrec, tiles, d_pack + blk.b.hdrs,
+                                      reinterpret_cast<JsExportScanStat*>(d_export_opt + keep.stats), d_tabs, d_export_opt + keep.hdrs, d_hdr_len, d_export_tmp + sc.cls, d_eob, d_blk_bits,
+                                      reinterpret_cast<JsRstSum*>(d_export_tmp + sc.sums), d_tile_off, reinterpret_cast<uint32_t*>(d_export_tmp + sc.res),
+                                      reinterpret_cast<uint64_t*>(d_export_tmp + sc.rec_bits))) {
+        js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
+    std::vector<uint8_t> back(sc.back2);
+    if (d2h_staged(back.data(), d_export_tmp, sc.back1)) return -1;                                  // ---- wait 1
+    const uint32_t* hdr_len = reinterpret_cast<const uint32_t*>(back.data() + sc.hdr_len);
+    std::vector<int> result((size_t)n); std::vector<uint32_t> detail((size_t)n);
+    uint64_t u_bytes = 0, out_bytes = 0;
+    if (pack_block(blk.b.total)) return -1;
+    if (js_export_prog_layout(recs, srecs, rec_base, n, unsupported.data(), reinterpret_cast<const uint32_t*>(back.data() + sc.res), reinterpret_cast<const uint64_t*>(back.data() + sc.rec_bits),
+                              hdr_len, chunk_base, result.data(), detail.data(), &u_bytes, &out_bytes)) return -1;
+    const uint32_t chunks = chunk_base[nrec];
+    if (chunks) {
+        const size_t ff_at = 0, off_at = ((size_t)chunks * 4 + 15u) & ~(size_t)15u, u_at = (off_at + (size_t)chunks * 8 + 15u) & ~(size_t)15u;
+        if (js_export_grow(&d_export_u, &d_export_u_cap, u_at + u_bytes) || js_export_grow(&d_export_out, &d_export_out_cap, out_bytes)) return -1;
+        if (pack_send(blk.b.total)) return -1;
+        HIP_TRY(hipMemsetAsync(d_export_u + u_at, 0, u_bytes, stream));
+        if (js_launch_export_prog_write(stream, dev.coef, dev.dccum, d_recs, d_srecs, reinterpret_cast<const uint32_t*>(d_pack + blk.b.unit_base), d_tile_base,
+                                        reinterpret_cast<const uint32_t*>(d_pack + blk.chunk_base), (uint32_t)n, (uint32_t)nrec, tiles, chunks, d_tabs, d_eob, d_blk_bits, d_tile_off,
+                                        reinterpret_cast<uint64_t*>(d_export_tmp + sc.itab), d_export_u + u_at, reinterpret_cast<uint32_t*>(d_export_u + ff_at),
+                                        reinterpret_cast<uint64_t*>(d_export_u + off_at), reinterpret_cast<uint64_t*>(d_export_tmp + sc.rec_ff), d_export_opt + keep.hdrs, d_hdr_len,
+                                        reinterpret_cast<uint64_t*>(d_export_tmp + sc.scan_out), d_export_out, reinterpret_cast<uint64_t*>(d_export_tmp + sc.len))) {
+            js_set_error("export_jpeg: launch failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
+        if (d2h_staged(back.data() + sc.len, d_export_tmp + sc.len, sc.back2 - sc.len)) return -1;     // ---- wait 2
+    } else memset(back.data() + sc.len, 0, sc.back2 - sc.len);
+    const uint64_t* len = reinterpret_cast<const uint64_t*>(back.data() + sc.len); const uint64_t* scan_out = reinterpret_cast<const uint64_t*>(back.data() + sc.scan_out);
+    const uint64_t* rec_ff = reinterpret_cast<const uint64_t*>(back.data() + sc.rec_ff);
+    for (int k = 0; k < n; k++) {
+        const JsImage& im = imgs[(size_t)(images ? images[k] : k)];
+        const std::vector<JsnoopExportScan>& script = im.ncomp == 1u ? script1 : script3;
+        JsExportEntry e; e.off = recs[k].out_off; e.len = recs[k].live ? len[k] : 0; e.result = result[(size_t)k]; e.detail = detail[(size_t)k]; e.image = images ? images[k] : k;
+        if (recs[k].live && (e.len < 4u || e.len > recs[k].out_cap)) {
+            exports.clear(); export_scans.clear(); export_scan_base.clear();
+            js_set_error("export_jpeg: entry %d came back with %llu bytes, its place holds %llu", k, (unsigned long long)e.len, (unsigned long long)recs[k].out_cap); return -1; }
+        export_scan_base.push_back((uint32_t)export_scans.size());
+        for (uint32_t i = rec_base[k]; recs[k].live && i < rec_base[k + 1]; i++) {
+            const JsExportScanRec& p = srecs[i];
+            JsExportScanInfo si; si.sc = script[p.scan]; si.ri = p.ri / p.spm; si.rec = i; si.ntab = p.ntab; si.kind = p.kind; si.intervals = p.ni;
+            si.sos_offset = scan_out[i] + hdr_len[i] - (8u + 2u * (uint32_t)__builtin_popcount(si.sc.comps)); si.data_bytes = (p.bits >> 3) + rec_ff[i] + 2u * (uint64_t)(p.ni - 1u);
+            export_scans.push_back(si);
+        }
+        if (recs[k].live) { const JsExportScanRec& p = srecs[rec_base[k]]; e.ri = p.ri / p.spm; e.intervals = p.ni; }
+        exports.push_back(e);
+    }
+    export_scan_base.push_back((uint32_t)export_scans.size());
+    export_prog = true; export_prog_nrec = nrec;
+    return 0;
+}
+
+int JsnoopBatch::export_scan_tables(int k, int scan, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq)
+{
+    if (k < 0 || (size_t)k >= exports.size()) { js_set_error("export_scan_tables: entry %d out of range, the last export holds %zu", k, exports.size()); return -1; }
+    if (!export_prog || !d_export_opt || export_scan_base.size() != exports.size() + 1) { js_set_error("export_scan_tables: the last export wrote no progressive files"); return -1; }
+    const int ns = (int)(export_scan_base[(size_t)k + 1] - export_scan_base[(size_t)k]);
+    if (!ns) { js_set_error("export_scan_tables: entry %d was not exported (result %d): it has no tables", k, exports[(size_t)k].result); return -1; }
+    if (scan < 0 || scan >= ns) { js_set_error("export_scan_tables: scan %d, entry %d has scans 0 .. %d", scan, k, ns - 1); return -1; }
+    const JsExportScanInfo& si = export_scans[export_scan_base[(size_t)k] + (size_t)scan];
+    if (slot < 0 || (uint32_t)slot >= si.ntab) { js_set_error("export_scan_tables: slot %d, scan %d of entry %d has %u tables", slot, scan, k, si.ntab); return -1; }
+    HIP_TRY(hipSetDevice(device));
+    const JsExportProgKeep keep = js_export_prog_keep(export_prog_nrec);
+    std::vector<JsExportScanStat> st(1);
+    if (d2h_staged(st.data(), d_export_opt + keep.stats + (size_t)si.rec * sizeof(JsExportScanStat), sizeof(JsExportScanStat))) return -1;
+    const JsExportOptSlot& s = st[0].slot[slot];
+    if (s.nsym > 256u) { js_set_error("export_scan_tables: entry %d, scan %d, slot %d came back with %u symbols", k, scan, slot, s.nsym); return -1; }
+    if (counts) memcpy(counts, s.counts, 16);
+    if (symbols) memcpy(symbols, s.syms, 256);
+    if (nsym) *nsym = s.nsym;
+    if (freq) {
+        memset(freq, 0, 256 * 4);
+        if (si.kind == JS_PROG_AC_FIRST) memcpy(freq, st[0].freq + 48, 256 * 4); else memcpy(freq, st[0].freq + slot * 16, 16 * 4);
     }
     return 0;
 }
@@ -263,9 +404,40 @@ int jsnoop_batch_export_restart(const JsnoopBatch* b, int k, uint32_t* ri, uint6
     if (intervals) *intervals = e->intervals;
     return 0;
 }
+void jsnoop_export_progressive_defaults(JsnoopExportProgressive* out) { if (out) js_export_progressive_defaults(out); }
+int jsnoop_batch_export_jpeg_prog(JsnoopBatch* b, const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const JsnoopExportProgressive* prog,
+                                  const int* images, int n)
+{
+    if (!b) { js_set_error("export_jpeg: batch is NULL"); return -1; }
+    return b->export_jpeg_prog(spec, coding, restart, prog, images, n);
+}
+int jsnoop_batch_export_scan_count(const JsnoopBatch* b, int k)
+{
+    if (!b || !b->export_prog || k < 0 || (size_t)k >= b->exports.size() || b->export_scan_base.size() != b->exports.size() + 1) return 0;
+    return (int)(b->export_scan_base[(size_t)k + 1] - b->export_scan_base[(size_t)k]);
+}
+int jsnoop_batch_export_scan_info(const JsnoopBatch* b, int k, int scan, JsnoopExportScan* sc, uint32_t* ri, uint64_t* intervals, uint64_t* sos_offset, uint64_t* data_bytes)
+{
+    if (!js_export_entry(b, k, "export_scan_info")) return -1;
+    const int ns = jsnoop_batch_export_scan_count(b, k);
+    if (scan < 0 || scan >= ns) { js_set_error("export_scan_info: scan %d, entry %d has %d scans", scan, k, ns); return -1; }
+    const JsnoopBatch::JsExportScanInfo& si = b->export_scans[b->export_scan_base[(size_t)k] + (size_t)scan];
+    if (sc) *sc = si.sc;
+    if (ri) *ri = si.ri;
+    if (intervals) *intervals = si.intervals;
+    if (sos_offset) *sos_offset = si.sos_offset;
+    if (data_bytes) *data_bytes = si.data_bytes;
+    return 0;
+}
+int jsnoop_batch_export_scan_tables(JsnoopBatch* b, int k, int scan, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256])
+{
+    if (!b) { js_set_error("export_scan_tables: batch is NULL"); return -1; }
+    return b->export_scan_tables(k, scan, slot, counts, symbols, nsym, freq);
+}
 int jsnoop_export_jpeg(JsnoopDecoder* d, const char* path) { return jsnoop_export_jpeg_rst(d, path, nullptr, nullptr); }
 int jsnoop_export_jpeg_coded(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding) { return jsnoop_export_jpeg_rst(d, path, coding, nullptr); }
-int jsnoop_export_jpeg_rst(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart)
+int jsnoop_export_jpeg_rst(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart) { return jsnoop_export_jpeg_prog(d, path, coding, restart, nullptr); }
+int jsnoop_export_jpeg_prog(JsnoopDecoder* d, const char* path, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const JsnoopExportProgressive* prog)
 {
     if (!d || !path) { js_set_error("jsnoop_export_jpeg: bad argument"); return -1; }
     if (!d->have_image || !d->preview_is_jpeg || !d->batch) { js_set_error("jsnoop_export_jpeg: no decoded image"); return -1; }
@@ -273,7 +445,7 @@ int jsnoop_export_jpeg_rst(JsnoopDecoder* d, const char* path, const JsnoopExpor
     JsnoopBatch* b = d->batch;
     JsnoopExportSpec spec; js_export_spec_defaults(&spec);
     const int img = d->img;
-    if (b->export_jpeg_rst(&spec, coding, restart, &img, 1)) return -1;
+    if (b->export_jpeg_prog(&spec, coding, restart, prog, &img, 1)) return -1;
     const JsExportEntry e = b->exports[0];
     if (e.result != JSNOOP_EXPORT_OK) { js_set_error("jsnoop_export_jpeg: not exported: %s, block %u", js_export_reason(e.result), e.detail); return -1; }
     std::vector<uint8_t> host((size_t)e.len);

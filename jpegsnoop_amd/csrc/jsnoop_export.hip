@@ -484,6 +484,7 @@ __device__ __forceinline__ uint64_t ex_wave_min(uint64_t v)
 // bit and the id c1 (what K.2's OTHERS chains do one link at a time).  Then lengths are counted, one lane runs Adjust_BITS (Figure K.3) and takes the reserved
 // code point off the longest length, the symbols are ranked by (code size, symbol) and get their Annex C codes.  The whole workgroup then puts the entry's header
 // together.  Every barrier is met by all four waves: a slot the image does not have runs along with nothing but the reserved symbol.
+// (k_prog_huff of jsnoop_export_prog.hip REPEATS this procedure for the progressive export's records: a fix to either belongs in both.)
 __global__ void __launch_bounds__(EX_THREADS) k_export_huff(const JsExportRec* __restrict__ recs, const JsExportOptRec* __restrict__ orecs, const uint32_t* __restrict__ unit_base,
                                                             const uint8_t* __restrict__ hdrs, JsExportOptStat* __restrict__ stats, uint32_t* __restrict__ tabs,
                                                             uint8_t* __restrict__ hdr_out, uint32_t* __restrict__ hdr_len)
@@ -663,5 +664,19 @@ int js_launch_export_write_rst(hipStream_t st, const int16_t* coef, const int16_
     hipLaunchKernelGGL(k_export_ffcount, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, chunk_base, nrec, (const uint8_t*)ustream, chunk_ff);
     hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, (const uint32_t*)chunk_ff, chunk_off, chunk_base, ent_ff);
     hipLaunchKernelGGL(k_export_stuff_rst, dim3(total_chunks), dim3(EX_THREADS), 0, st, recs, rrecs, chunk_base, nrec, (const uint8_t*)ustream, (const uint64_t*)chunk_off, (const uint64_t*)itab, hdrs, out, len);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- jsnoop_batch_export_jpeg_prog (jsnoop_export_prog.hip) places its tiles and chunks with the two scan kernels above, one "entry" per (entry, scan) record
+int js_launch_export_scan(hipStream_t st, const uint32_t* cnt, uint64_t* off, const uint32_t* base, uint32_t nrec, uint64_t* total)
+{
+    if (!nrec) return 0;
+    hipLaunchKernelGGL(k_export_scan, dim3(nrec), dim3(EX_THREADS), 0, st, cnt, off, base, total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int js_launch_export_rst_scan(hipStream_t st, const JsRstSum* sum, uint64_t* off, const uint32_t* base, uint32_t nrec, uint64_t* total)
+{
+    if (!nrec) return 0;
+    hipLaunchKernelGGL(k_export_rst_scan, dim3(nrec), dim3(EX_THREADS), 0, st, sum, off, base, total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -147,6 +147,14 @@ struct JsnoopBatch {
     int  export_jpeg_rst(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const int* images, int n);
     int  export_tables(int k, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq);
     uint8_t* d_export_opt = nullptr; size_t d_export_opt_cap = 0; bool export_opt = false;
+    // jsnoop_batch_export_jpeg_prog: progressive files along a scan script (jsnoop_export_prog_check.h; kernels: jsnoop_export_prog.hip).  mode OFF is export_jpeg_rst;
+    // otherwise every (entry, scan) is a record of its own, the scans' tables and header pieces are built on the device (d_export_opt holds them for
+    // export_scan_tables) and a file is its scans' pieces one behind the other.  export_prog says the last export was of this kind; export_scans: what
+    // jsnoop_batch_export_scan_info reports, the scans of entry k at [export_scan_base[k], export_scan_base[k + 1]) (none for an entry without a file).
+    int  export_jpeg_prog(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const JsnoopExportProgressive* prog, const int* images, int n);
+    int  export_scan_tables(int k, int scan, int slot, uint8_t* counts, uint8_t* symbols, uint32_t* nsym, uint32_t* freq);
+    struct JsExportScanInfo { JsnoopExportScan sc; uint32_t ri, rec, ntab, kind; uint64_t intervals, sos_offset, data_bytes; };
+    bool export_prog = false; size_t export_prog_nrec = 0; std::vector<JsExportScanInfo> export_scans; std::vector<uint32_t> export_scan_base;
     struct JsExportEntry { uint64_t off, len; int result; uint32_t detail; int image; uint32_t ri = 0; uint64_t intervals = 0; };   // entry k of the last export: its file at d_export_out + off
     std::vector<JsExportEntry> exports;
     uint8_t* d_export_tmp = nullptr; size_t d_export_tmp_cap = 0; // scratch of the first phase: result words, bit lengths per block / tile / entry

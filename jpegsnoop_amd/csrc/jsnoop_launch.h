@@ -145,6 +145,21 @@ int  js_launch_export_measure_rst(hipStream_t st, const int16_t* coef, const int
 int  js_launch_export_write_rst(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportRstRec* rrecs, const uint32_t* unit_base,
                                 const uint32_t* chunk_base, uint32_t nrec, uint32_t total_units, uint32_t total_chunks, const uint32_t* tabs, uint32_t tab_stride, const uint16_t* blk_bits,
                                 const uint64_t* unit_off, uint64_t* itab, uint8_t* ustream, uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* ent_ff, const uint8_t* hdrs, uint8_t* out, uint64_t* len);
+// jsnoop_batch_export_jpeg_prog (progressive files; jsnoop_export_prog.hip): a record per (entry, scan) of the coded entries (srecs, nrec of them; rec_base: the
+// entries' prefix table over them, tile_base / chunk_base: theirs over tiles of JS_EXPORT_TILE units / chunks of the scans' un-stuffed streams).  First phase:
+// k_prog_classify, k_prog_runs (the carried end-of-band run of every unit), k_prog_symbols, k_prog_huff (stats, zeroed by the caller; the scans' code words at
+// tabs + i * JS_PROG_TAB_WORDS, header pieces at hdr_out + i * JS_PROG_HDR, their lengths), k_prog_measure, k_export_rst_scan over the tiles of every record.
+// Second phase: k_prog_bits into the zeroed streams, k_prog_ffcount, k_export_scan, k_prog_place (scan_out: where a scan's piece starts in its file; len: zeroed
+// by the caller), k_prog_stuff.  0, -1 on a launch error.  js_launch_export_scan / _rst_scan: the two scan kernels of jsnoop_export.hip over any prefix table.
+int  js_launch_export_scan(hipStream_t st, const uint32_t* cnt, uint64_t* off, const uint32_t* base, uint32_t nrec, uint64_t* total);
+int  js_launch_export_rst_scan(hipStream_t st, const JsRstSum* sum, uint64_t* off, const uint32_t* base, uint32_t nrec, uint64_t* total);
+int  js_launch_export_prog_measure(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportScanRec* srecs, const uint32_t* tile_base, uint32_t nent,
+                                   uint32_t nrec, uint32_t tiles, const uint8_t* hdrs, JsExportScanStat* stats, uint32_t* tabs, uint8_t* hdr_out, uint32_t* hdr_len, uint8_t* cls, uint16_t* eob,
+                                   uint16_t* blk_bits, JsRstSum* tile_sum, uint64_t* tile_off, uint32_t* res, uint64_t* rec_bits);
+int  js_launch_export_prog_write(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsExportRec* recs, const JsExportScanRec* srecs, const uint32_t* rec_base, const uint32_t* tile_base,
+                                 const uint32_t* chunk_base, uint32_t nent, uint32_t nrec, uint32_t tiles, uint32_t chunks, const uint32_t* tabs, const uint16_t* eob, const uint16_t* blk_bits,
+                                 const uint64_t* tile_off, uint64_t* itab, uint8_t* ustream, uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* rec_ff, const uint8_t* hdrs,
+                                 const uint32_t* hdr_len, uint64_t* scan_out, uint8_t* out, uint64_t* len);
 // jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
 // head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
 // the two totals as 64-bit words).  0, -1 on a launch error.

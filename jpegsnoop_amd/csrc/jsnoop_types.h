@@ -210,6 +210,28 @@ struct JsExportRstRec { uint64_t itab_off; uint32_t ri_blocks, ni; };
 // The summary of a run of blocks under that rule: has -- an interval ends inside the run; head -- the bits in front of the first such end (all bits where has
 // is 0); mid -- whole bytes between the first and the last end; tail -- the bits behind the last end.  js_rst_combine (jsnoop_export_rst_check.h) is associative.
 struct JsRstSum { uint32_t has, head, mid, tail; };
+// jsnoop_batch_export_jpeg_prog (progressive files; arithmetic: jsnoop_export_prog_check.h, kernels: jsnoop_export_prog.hip): one record per (entry, scan) of the
+// entries that are coded, beside the entry's JsExportRec (which holds the arena's place and the multipliers).  A unit is one block of the scan in the scan's own
+// order; unit u is arena block (u / spm) * bpm + pos[u % spm] of the entry in an interleaved scan (and in every scan of a one-component image: spm = bpm = 1),
+// and block (bx, by) = (u % w, u / w) of the component's coded part in a one-component scan of a three-component image (single = 1):
+// ((by / V) * mcu_x + bx / H) * bpm + base + (by % V) * H + bx % H.  back[p]: how many units back the unit of the same component before position p lies.
+// kind: JS_PROG_DC_FIRST / _DC_REFINE / _AC_FIRST; ri: the scan's restart interval in UNITS (0: one interval), ni its intervals; ubase: the scan's first unit in
+// the call's per-unit arrays; ntab tables (a DC first scan: one per scan component, slot = position in the scan; an AC scan: one); the scan's header piece is
+// pre (hdrs + pre_off, pre_len bytes: the file up to SOF2 for the first scan, else nothing), the DHT segments the device builds, post (DRI where Ri changes, SOS).
+// Phase 2 fills live, bits (the scan's un-stuffed stream: every interval padded), u_off.
+#define JS_PROG_DC_FIRST  0u
+#define JS_PROG_DC_REFINE 1u
+#define JS_PROG_AC_FIRST  2u
+#define JS_PROG_TAB_WORDS 304u       /* DC slot 0..2 [16] each, AC [256] */
+#define JS_PROG_HDR       768u       /* a scan's header piece on the device: 438 up to SOF at most, 3 x (21 + 16) or 21 + 256 of DHT, DRI 6, SOS 14 */
+#define JS_PROG_POST      32u
+struct JsExportScanRec { uint64_t ubase, itab_off, bits, u_off; uint32_t entry, scan, nunits, ri, ni, kind, ss, se, al, single, w, H, V, mcu_x, bpm, base, spm, ntab,
+                    pre_off, pre_len, post_off, post_len, live, comp0;
+                    uint8_t pos[JS_MAX_BLK_PER_MCU], comp[JS_MAX_BLK_PER_MCU], slot[JS_MAX_BLK_PER_MCU], back[JS_MAX_BLK_PER_MCU]; };
+struct JsExportScanStat { uint32_t freq[JS_PROG_TAB_WORDS]; JsExportOptSlot slot[3]; };
+// The summaries of the two segmented scans that resolve end-of-band runs (operators and proofs: jsnoop_export_prog_check.h).
+struct JsRunFwd { uint32_t cnt, cut, tail; };    // units behind the last cut (all where cut is 0); a cut lies inside; the last cut was a block with symbols whose band ends in zeros
+struct JsRunBwd { uint32_t lead, open; };        // empty units from the front up to the first stop; no stop inside
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

@@ -83,11 +83,17 @@ class CimgDecode:
     def ExportTiff(self, path: str, nMode: int = 0) -> bool:
         return self._lib.jsnoop_export_tiff(self._h, path.encode(), nMode) == 0
 
-    def export_jpeg(self, path: str, huffman: str = "annex_k", restart=0) -> bool:
+    def export_jpeg(self, path: str, huffman: str = "annex_k", restart=0, progressive=False) -> bool:
         """The decoded image written back as a baseline JPEG file (jsnoop_export_jpeg): the coefficients the decoder holds, entropy-coded on the
         device.  False, and no file, where the image cannot be exported (capi.last_error() has the reason).  huffman="optimal": with the image's own
-        Huffman tables (jsnoop_export_jpeg_coded).  restart: as in JpegBatch.export_jpeg (jsnoop_export_jpeg_rst)."""
+        Huffman tables (jsnoop_export_jpeg_coded).  restart: as in JpegBatch.export_jpeg (jsnoop_export_jpeg_rst).  progressive: False (the default) writes
+        a baseline file; True a progressive (SOF2) file along the built-in scan script; a list of scans (components, ss, se, ah, al) along that script, as
+        in JpegBatch.export_jpeg (jsnoop_export_jpeg_prog): every scan then has its own optimal tables whatever huffman says, and restart counts in each
+        scan's own units."""
         rst = capi.export_restart(self._lib, restart)
+        prog = capi.export_progressive(self._lib, progressive)
+        if prog.mode != capi.PROGRESSIVE_OFF:
+            return self._lib.jsnoop_export_jpeg_prog(self._h, path.encode(), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst), C.byref(prog)) == 0
         if rst.mode != capi.RESTART_NONE:
             return self._lib.jsnoop_export_jpeg_rst(self._h, path.encode(), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst)) == 0
         if huffman == "annex_k":
@@ -838,19 +844,23 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_log(self._h, i, int(histo_en), int(stat_clip_en), int(quiet), cb, None), "batch_log")
         return out
 
-    def _export(self, images, jfif, what, huffman="annex_k", restart=0):
+    def _export(self, images, jfif, what, huffman="annex_k", restart=0, progressive=False):
         n_all = len(self)
         idx = list(range(n_all)) if images is None else [int(i) for i in images]
         for i in idx:
             if not 0 <= i < n_all:
                 raise IndexError(f"{what}: image index {i} out of range, the batch holds {n_all}")
         rst = capi.export_restart(self._lib, restart)                 # (refuses what is no restart value before anything is done)
+        prog = capi.export_progressive(self._lib, progressive)
         spec = capi.ExportSpec()
         self._lib.jsnoop_export_spec_defaults(C.byref(spec))
         spec.jfif = 1 if jfif else 0
         self.sync()
         ind = (C.c_int * max(len(idx), 1))(*idx)
-        if rst.mode != capi.RESTART_NONE:
+        if prog.mode != capi.PROGRESSIVE_OFF:
+            self._chk(self._lib.jsnoop_batch_export_jpeg_prog(self._h, C.byref(spec), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst), C.byref(prog), ind, len(idx)),
+                      "batch_export_jpeg_prog")
+        elif rst.mode != capi.RESTART_NONE:
             self._chk(self._lib.jsnoop_batch_export_jpeg_rst(self._h, C.byref(spec), C.byref(capi.export_coding(self._lib, huffman)), C.byref(rst), ind, len(idx)),
                       "batch_export_jpeg_rst")
         elif huffman == "annex_k":
@@ -879,6 +889,34 @@ class JpegBatch:
         self._chk(self._lib.jsnoop_batch_export_restart(self._h, int(k), C.byref(ri), C.byref(n)), "batch_export_restart")
         return int(ri.value), int(n.value)
 
+    def export_scans(self, k):
+        """Entry k of the last export_jpeg(progressive=...): one dict per scan of its file with comps (list of component indices), ss, se, ah, al, ri (the
+        scan's restart interval in its own units), intervals, sos_offset (where its SOS marker stands in the file) and data_bytes (its entropy-coded
+        data, stuffing and RSTn included); empty for a baseline or absent file (jsnoop_batch_export_scan_info)."""
+        out = []
+        for i in range(self._lib.jsnoop_batch_export_scan_count(self._h, int(k))):
+            sc, ri, n, sos, nb = capi.ExportScan(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            self._chk(self._lib.jsnoop_batch_export_scan_info(self._h, int(k), i, C.byref(sc), C.byref(ri), C.byref(n), C.byref(sos), C.byref(nb)), "batch_export_scan_info")
+            out.append(dict(comps=[c for c in range(8) if sc.comps >> c & 1], ss=sc.ss, se=sc.se, ah=sc.ah, al=sc.al, ri=int(ri.value), intervals=int(n.value),
+                            sos_offset=int(sos.value), data_bytes=int(nb.value)))
+        return out
+
+    def export_scan_tables(self, k, scan):
+        """The Huffman tables the device built for scan `scan` of entry k of the last progressive export: one dict per table (a DC first scan: one per scan
+        component, in the scan's order; an AC scan: one; a refinement scan: none) with freq, counts and symbols as export_tables returns them
+        (jsnoop_batch_export_scan_tables)."""
+        scans = self.export_scans(k)
+        if not 0 <= scan < len(scans):
+            raise IndexError(f"export_scan_tables: scan {scan}, entry {k} has {len(scans)} scans")
+        sc = scans[scan]
+        ntab = 1 if sc["ss"] else (len(sc["comps"]) if sc["ah"] == 0 else 0)
+        out = []
+        for slot in range(ntab):
+            counts, syms, freq, n = (C.c_uint8 * 16)(), (C.c_uint8 * 256)(), (C.c_uint32 * 256)(), C.c_uint32()
+            self._chk(self._lib.jsnoop_batch_export_scan_tables(self._h, int(k), int(scan), slot, counts, syms, C.byref(n), freq), "batch_export_scan_tables")
+            out.append(dict(slot=slot, freq=list(freq), counts=list(counts), symbols=list(syms[:n.value])))
+        return out
+
     def export_results(self):
         """The entries of the last export_jpeg / export_jpeg_to_torch, in the order of its list: dicts with image, result (capi.EXPORT_OK / _INEXACT /
         _UNCODABLE / _UNSUPPORTED), detail (the lowest offending block of the image, decode order; 0 where the result has none), len (0 unless OK)
@@ -890,7 +928,7 @@ class JpegBatch:
             out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
         return out
 
-    def export_jpeg(self, images=None, jfif=True, huffman="annex_k", restart=0):
+    def export_jpeg(self, images=None, jfif=True, huffman="annex_k", restart=0, progressive=False):
         """What the batch holds for the listed images (None = all; any order, repeats allowed) written back as baseline JPEG files, entropy-coded on
         the device by ONE jsnoop_batch_export_jpeg: a list with the file's bytes per entry, None where the image could not be exported
         (export_results() says why).  An exported file decodes to the same coefficients; where the source was a clean file, to the same pixels.
@@ -899,9 +937,12 @@ class JpegBatch:
         image's symbol counts (export_tables(k) returns them); "annex_k" (the default): the tables of T.81 Annex K.  restart: 0 (the default) writes no
         restart markers; an int the interval in MCUs; ("rows", n) n MCU rows of each image; "source" the interval each image was decoded with (none where it
         had none).  With an interval the files carry DRI and FF D0..D7 between the intervals (jsnoop_batch_export_jpeg_rst; export_restart(k) says what entry
-        k got); an image whose interval comes out above 65535 is not exported (capi.EXPORT_UNSUPPORTED)."""
+        k got); an image whose interval comes out above 65535 is not exported (capi.EXPORT_UNSUPPORTED).  progressive: False (the default) writes
+        baseline files; True progressive (SOF2) files along the built-in scan script; a list of scans (components, ss, se, ah, al) along that script
+        (jsnoop_batch_export_jpeg_prog; DESIGN.md 4.17 has the rules, a script that breaks one is refused).  Every scan then carries its own optimal
+        tables whatever huffman says, restart counts in each scan's own units, and export_scans(k) / export_scan_tables(k, scan) describe the file."""
         files = []
-        for k, e in enumerate(self._export(images, jfif, "export_jpeg", huffman, restart)):
+        for k, e in enumerate(self._export(images, jfif, "export_jpeg", huffman, restart, progressive)):
             if not e["len"]:
                 files.append(None); continue
             buf = (C.c_uint8 * e["len"])()
@@ -911,12 +952,12 @@ class JpegBatch:
             files.append(bytes(buf))
         return files
 
-    def export_jpeg_to_torch(self, images=None, jfif=True, huffman="annex_k", restart=0):
+    def export_jpeg_to_torch(self, images=None, jfif=True, huffman="annex_k", restart=0, progressive=False):
         """export_jpeg, but the files stay on the device: a list with one uint8 tensor per entry (None where the image could not be exported), copied
         out of the batch's memory by jsnoop_batch_export_copy -- they outlive the next export."""
         import torch
         dev = torch.device("cuda", self.device())
-        res = self._export(images, jfif, "export_jpeg_to_torch", huffman, restart)
+        res = self._export(images, jfif, "export_jpeg_to_torch", huffman, restart, progressive)
         sizes = [-(-e["len"] // 16) * 16 for e in res]
         flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
         cur = torch.cuda.current_stream(dev)
