@@ -3,7 +3,8 @@
 encode_baseline codes coefficient arrays with optimal tables and asserts away what a conforming encoder never writes.  `write`
 takes the Huffman tables as they are handed in and, per block, either 64 coefficients (zig-zag order, absolute DC) or the block's
 tokens themselves: [(DC category, difference), (AC symbol, value), ...].  The token form may hold DC categories 12..15, AC sizes
-11..15, `run/0` symbols with run 1..14, ZRL anywhere, runs that carry the index past 63 and blocks that end without EOB.
+11..15, `run/0` symbols with run 1..14, ZRL anywhere, runs that carry the index past 63 and blocks that end without EOB.  A token
+(BITS, (value, n)) writes n literal bits -- a code that matches nothing, value bits that are cut off: what no table can express.
 
 Besides the file `write` returns a CENSUS: one record per Huffman symbol with the bit position of its code in the un-stuffed entropy
 data (restart markers removed, the pad bits in front of them kept: the layout the parallel path cuts into sub-sequences), the
@@ -22,6 +23,7 @@ L1_BITS = 9            # JS_L1_BITS   (jpegsnoop_amd/csrc/jsnoop_types.h)
 LUT2_MAX = 2048        # JS_LUT2_MAX
 
 Rec = namedtuple("Rec", "pos iv blk k tab len size sym")
+BITS = "bits"          # the symbol of a literal-bits token; its census record: tab None, len 0, size n
 
 
 class Stream:
@@ -61,6 +63,8 @@ def tokens_of(vec, pred):
 def coefs_of(tokens, pred):
     """What a conforming decoder makes of a block's tokens, or None when the tokens are not conforming (run/0, overshoot, ...)."""
     out = [0] * 64
+    if any(t[0] == BITS for t in tokens):
+        return None
     s, d = tokens[0]
     if s > 11:
         return None
@@ -114,9 +118,13 @@ def write(frame, tabs, comp_ids, blocks, dri=0, rst_before=()):
             T = list(blk) if is_tokens else tokens_of(blk, pred[c])
             want = coefs_of(T, pred[c])
             coefs.append(want)
-            pred[c] += int(T[0][1]) if T[0][0] else 0
+            pred[c] += int(T[0][1]) if T[0][0] and T[0][0] != BITS else 0
             k = 0
             for n, (sym, v) in enumerate(T):
+                if sym == BITS:
+                    census.append(Rec(base + nb, iv, bi, k, None, 0, int(v[1]), BITS))
+                    w.put(int(v[0]), int(v[1])); nb += int(v[1])
+                    continue
                 key = (0 if n == 0 else 1, comp_ids[c][0 if n == 0 else 1])
                 code, ln = codes[key][sym]
                 size = sym & 15
