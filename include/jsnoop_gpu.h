@@ -725,6 +725,67 @@ int          jsnoop_batch_export_scan_info(const JsnoopBatch*, int k, int scan, 
 int          jsnoop_batch_export_scan_tables(JsnoopBatch*, int k, int scan, int slot, uint8_t counts[16], uint8_t symbols[256], uint32_t* nsym, uint32_t freq[256]);
 int          jsnoop_export_jpeg_prog(JsnoopDecoder*, const char* path, const JsnoopExportCoding*, const JsnoopExportRestart*, const JsnoopExportProgressive*);
 
+/* ---- encode: pixels in device memory to JPEG files, on the device ---------------------------------------------------------------------------
+ * The forward path in front of the export: colour conversion, chroma downsampling, forward DCT and quantisation of 8-bit pictures that lie in
+ * device memory -- what jsnoop_batch_pack wrote, a batch's own DIB, any tensor -- into a coefficient arena and a cumulative-DC array of the form a
+ * decode leaves, which the export above then writes as files, unchanged.  The arithmetic is libjpeg's integer path ("islow" DCT), exactly:
+ * tests/encode_model.py is the definition, value for value; DESIGN.md section 4.18 has the contract (colour constants, padding and downsampling rules,
+ * the quantiser's rounding, the dummy-block rule).
+ *
+ * A JsnoopEncode owns its arena, its export memory and (unless the caller passes one) its stream; it lives on the device that was current when it
+ * was created.  jsnoop_encode_run encodes n pictures in ONE launch on that stream, waits for nothing, and replaces what the object held:
+ * picture i of the call is image i of the object until the next successful run.  A picture has 1 channel (grey: one component, 1 x 1) or 3; the
+ * spec applies to the whole call:
+ *   subsampling  JSNOOP_ENCODE_444 / _422 / _420: luma H x V = 1x1 / 2x1 / 2x2, chroma 1 x 1 (a grey picture ignores it).
+ *   qtables      NULL: the tables come from `quality` (1..100): scale = quality < 50 ? 5000 / quality : 200 - 2 quality,
+ *                v = clamp((base * scale + 50) / 100, 1, 255) over T.81 Tables K.1 / K.2.  Else 128 bytes, luma[64] then chroma[64], natural
+ *                order, every value 1..255, taken as they are (quality is then not read).  jsnoop_encode_qtables: the tables a spec comes to.
+ * A source: sample (x, y) of channel c lies at ptr + y' * row_pitch + x * pixel_stride + c' (INTERLEAVED) or ptr + c' * plane_pitch + y' * row_pitch +
+ * x * pixel_stride (PLANAR); c' = c for JSNOOP_ENCODE_RGB and 2 - c for _BGR (a grey picture: 0); y' = y, or height - 1 - y with bottom_up (a DIB:
+ * INTERLEAVED, BGR, pixel_stride 4, bottom_up 1).  0 stands for the dense value of pixel_stride (channels, or 1 when PLANAR), row_pitch
+ * (width * pixel_stride) and plane_pitch (height * row_pitch).  Any byte alignment is accepted.  Only addressed bytes are read.
+ *
+ * What a run leaves: arena rows [blocks][64] int16 in decode order, natural order inside a row, slot n = level * q[n], slot 0 = 0; dccum[b] = DC
+ * level * q[0].  No product wraps (|value| < 1154).  jsnoop_encode_image_info returns the words of jsnoop_batch_image_info; jsnoop_encode_read_coefs
+ * copies up to max_blocks rows and dccum values to the host (waits; either pointer may be NULL) and returns the number copied.
+ * jsnoop_encode_export is jsnoop_batch_export_jpeg_prog on the encoded arena: every mode, result word and limit of that call (NULL coding, restart
+ * or progressive: the defaults; JSNOOP_RESTART_SOURCE finds no interval); jsnoop_encode_export_count, _export_file, _read_export, _export_copy,
+ * _export_scan_count and _export_scan_info are the batch calls of the same name.  The files stay valid until the next export, run or destroy.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, the previous result untouched: a NULL object, spec or (n > 0) source list; n < 0; a
+ * struct_size that is too small or larger than this library's (read like JsnoopPackSpec's); quality outside 1..100 without tables; a table value
+ * of 0; an unknown subsampling, layout or order; non-zero reserved fields; a NULL ptr; width or height outside 1..65535; channels other than 1 or
+ * 3; a pixel_stride below the channel count (1 when PLANAR), a row_pitch below width * pixel_stride, a plane_pitch below height * row_pitch;
+ * bottom_up other than 0 / 1; 2^31 units of work or more in one call.  An export refuses, before it touches the previous export, what
+ * jsnoop_batch_export_jpeg_prog refuses, an object that has not run, and an image index out of range.                                        */
+#define JSNOOP_ENCODE_444         0
+#define JSNOOP_ENCODE_422         1
+#define JSNOOP_ENCODE_420         2
+#define JSNOOP_ENCODE_INTERLEAVED 0
+#define JSNOOP_ENCODE_PLANAR      1
+#define JSNOOP_ENCODE_RGB         0
+#define JSNOOP_ENCODE_BGR         1
+#define JSNOOP_ENCODE_RUN         8u       /* MCUs of one MCU row a wave encodes at a time (k_encode), for tests that place widths at its seams */
+typedef struct JsnoopEncode JsnoopEncode;
+typedef struct JsnoopEncodeSpec { uint32_t struct_size; int32_t quality, subsampling; uint32_t reserved; const uint8_t* qtables; } JsnoopEncodeSpec;
+typedef struct JsnoopEncodeSrc  { const void* ptr; uint32_t width, height, channels; int32_t layout, order; uint32_t pixel_stride; uint64_t row_pitch, plane_pitch;
+                                  uint32_t bottom_up, reserved; } JsnoopEncodeSrc;                 /* device pointer; pitches in bytes, 0 = dense */
+JsnoopEncode* jsnoop_encode_create(void* stream);                                                 /* NULL stream: a stream of its own */
+void         jsnoop_encode_destroy(JsnoopEncode*);
+void         jsnoop_encode_spec_defaults(JsnoopEncodeSpec* out);                                   /* quality 75, 4:2:0, no tables; NULL tolerated */
+int          jsnoop_encode_qtables(const JsnoopEncodeSpec*, uint8_t luma64[64], uint8_t chroma64[64]);   /* host arithmetic, natural order; 0 / -1 */
+int          jsnoop_encode_run(JsnoopEncode*, const JsnoopEncodeSpec*, const JsnoopEncodeSrc* src, int n);
+int          jsnoop_encode_count(const JsnoopEncode*);
+int          jsnoop_encode_image_info(const JsnoopEncode*, int i, unsigned* out16);
+int          jsnoop_encode_read_coefs(JsnoopEncode*, int i, int16_t* coefs, int16_t* dccum, size_t max_blocks);
+int          jsnoop_encode_export(JsnoopEncode*, const JsnoopExportSpec*, const JsnoopExportCoding*, const JsnoopExportRestart*, const JsnoopExportProgressive*, const int* images, int n);
+int          jsnoop_encode_export_count(const JsnoopEncode*);
+int          jsnoop_encode_export_file(const JsnoopEncode*, int k, const void** dev_ptr, uint64_t* len, int* result, uint32_t* detail, int* image);
+int64_t      jsnoop_encode_read_export(JsnoopEncode*, int k, void* host_dst, uint64_t cap);
+int64_t      jsnoop_encode_export_copy(JsnoopEncode*, int k, void* dev_dst, uint64_t cap);
+int          jsnoop_encode_export_scan_count(const JsnoopEncode*, int k);
+int          jsnoop_encode_export_scan_info(const JsnoopEncode*, int k, int scan, JsnoopExportScan* sc, uint32_t* ri, uint64_t* intervals, uint64_t* sos_offset, uint64_t* data_bytes);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

@@ -226,6 +226,44 @@ def export_progressive(lib, progressive):
     return p
 
 
+ENCODE_444, ENCODE_422, ENCODE_420 = 0, 1, 2
+ENCODE_SUBSAMPLING = {"4:4:4": ENCODE_444, "4:2:2": ENCODE_422, "4:2:0": ENCODE_420, 0: ENCODE_444, 1: ENCODE_422, 2: ENCODE_420}
+ENCODE_INTERLEAVED, ENCODE_PLANAR = 0, 1
+ENCODE_RGB, ENCODE_BGR = 0, 1
+ENCODE_RUN = 8          # JSNOOP_ENCODE_RUN of include/jsnoop_gpu.h: MCUs of one MCU row a wave encodes at a time
+
+
+class EncodeSpec(C.Structure):
+    """JsnoopEncodeSpec of include/jsnoop_gpu.h: quality or tables, and the chroma subsampling, of one jsnoop_encode_run."""
+    _fields_ = [("struct_size", C.c_uint32), ("quality", C.c_int32), ("subsampling", C.c_int32), ("reserved", C.c_uint32), ("qtables", C.POINTER(C.c_uint8))]
+
+
+class EncodeSrc(C.Structure):
+    """JsnoopEncodeSrc of include/jsnoop_gpu.h: one 8-bit picture in device memory (pitches in bytes, 0 = dense)."""
+    _fields_ = [("ptr", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("layout", C.c_int32), ("order", C.c_int32),
+                ("pixel_stride", C.c_uint32), ("row_pitch", C.c_uint64), ("plane_pitch", C.c_uint64), ("bottom_up", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def encode_spec(lib, quality=75, subsampling="4:2:0", qtables=None):
+    """The JsnoopEncodeSpec of quality 1..100 | qtables = (luma64, chroma64) in natural order, and subsampling "4:4:4" | "4:2:2" | "4:2:0" (or 0 | 1 | 2).
+    Values are handed to the library as given: it refuses what is out of range.  The struct keeps the table bytes alive (._tables)."""
+    if subsampling not in ENCODE_SUBSAMPLING:
+        raise ValueError('subsampling must be "4:4:4", "4:2:2" or "4:2:0", not %r' % (subsampling,))
+    s = EncodeSpec()
+    lib.jsnoop_encode_spec_defaults(C.byref(s))
+    s.quality = int(quality); s.subsampling = ENCODE_SUBSAMPLING[subsampling]
+    if qtables is not None:
+        try:
+            luma, chroma = ([int(v) for v in t] for t in qtables)
+            if len(luma) != 64 or len(chroma) != 64 or not all(0 <= v <= 255 for v in luma + chroma):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("qtables must be two tables of 64 values 1..255 (luma, chroma), natural order") from None
+        arr = (C.c_uint8 * 128)(*(luma + chroma))
+        s.qtables = C.cast(arr, C.POINTER(C.c_uint8)); s._tables = arr
+    return s
+
+
 CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
 CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
 CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
@@ -411,6 +449,21 @@ SIGNATURES = {
     "jsnoop_batch_export_scan_info": (_i, [_p, _i, _i, C.POINTER(ExportScan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jsnoop_batch_export_scan_tables": (_i, [_p, _i, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "jsnoop_export_jpeg_prog": (_i, [_p, C.c_char_p, C.POINTER(ExportCoding), C.POINTER(ExportRestart), C.POINTER(ExportProgressive)]),
+    "jsnoop_encode_create": (_p, [_p]),
+    "jsnoop_encode_destroy": (None, [_p]),
+    "jsnoop_encode_spec_defaults": (None, [C.POINTER(EncodeSpec)]),
+    "jsnoop_encode_qtables": (_i, [C.POINTER(EncodeSpec), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "jsnoop_encode_run": (_i, [_p, C.POINTER(EncodeSpec), C.POINTER(EncodeSrc), _i]),
+    "jsnoop_encode_count": (_i, [_p]),
+    "jsnoop_encode_image_info": (_i, [_p, _i, _PU]),
+    "jsnoop_encode_read_coefs": (_i, [_p, _i, C.POINTER(C.c_int16), C.POINTER(C.c_int16), _sz]),
+    "jsnoop_encode_export": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), C.POINTER(ExportRestart), C.POINTER(ExportProgressive), _PI, _i]),
+    "jsnoop_encode_export_count": (_i, [_p]),
+    "jsnoop_encode_export_file": (_i, [_p, _i, C.POINTER(_p), C.POINTER(C.c_uint64), _PI, C.POINTER(C.c_uint32), _PI]),
+    "jsnoop_encode_read_export": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_encode_export_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_encode_export_scan_count": (_i, [_p, _i]),
+    "jsnoop_encode_export_scan_info": (_i, [_p, _i, _i, C.POINTER(ExportScan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

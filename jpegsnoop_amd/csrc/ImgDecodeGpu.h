@@ -287,6 +287,26 @@ public:
       if (!bOptimal) return jsnoop_batch_export_jpeg(m_b, &spec, p, n) == 0;
       JsnoopExportCoding coding; jsnoop_export_coding_defaults(&coding); coding.huffman = JSNOOP_HUFFMAN_OPTIMAL;
       return jsnoop_batch_export_jpeg_coded(m_b, &spec, &coding, p, n) == 0; }
+    // the forward path: 8-bit pictures in device memory (what BatchPack wrote, a DIB, any buffer: JsnoopEncodeSrc) to JPEG files, transformed, quantised and
+    // entropy-coded on the current device (jsnoop_encode_run + jsnoop_encode_export on an encoder object of its own; jsnoop_encode_spec_defaults fills a spec).
+    // files[k]: the file of src[k], empty where it could not be written.  pCoding / pRestart / pProg: NULL = Annex K tables, no restart markers, baseline.
+    static bool EncodeJpeg(const std::vector<JsnoopEncodeSrc>& src, const JsnoopEncodeSpec& spec, std::vector<std::vector<uint8_t>>& files, bool bJfif = true,
+                           const JsnoopExportCoding* pCoding = nullptr, const JsnoopExportRestart* pRestart = nullptr, const JsnoopExportProgressive* pProg = nullptr)
+    {
+        files.clear();
+        JsnoopEncode* e = jsnoop_encode_create(nullptr);
+        if (!e) return false;
+        JsnoopExportSpec ex; jsnoop_export_spec_defaults(&ex); ex.jfif = bJfif ? 1 : 0;
+        bool ok = jsnoop_encode_run(e, &spec, src.data(), (int)src.size()) == 0 && jsnoop_encode_export(e, &ex, pCoding, pRestart, pProg, nullptr, (int)src.size()) == 0;
+        for (int k = 0; ok && k < jsnoop_encode_export_count(e); k++) {
+            uint64_t nLen = 0;
+            ok = jsnoop_encode_export_file(e, k, nullptr, &nLen, nullptr, nullptr, nullptr) == 0;
+            files.emplace_back((size_t)nLen);
+            if (ok && nLen) ok = jsnoop_encode_read_export(e, k, files.back().data(), nLen) == (int64_t)nLen;
+        }
+        jsnoop_encode_destroy(e);
+        return ok;
+    }
     // BatchExportJpeg with a restart interval per file (jsnoop_batch_export_jpeg_rst): nMode JSNOOP_RESTART_*, nInterval in MCUs or MCU rows; BatchExportRestart: what entry k got
     bool     BatchExportJpegRestart(const std::vector<int>& files, bool bJfif, bool bOptimal, int nMode, unsigned nInterval)
     { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;

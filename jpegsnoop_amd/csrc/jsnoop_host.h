@@ -206,6 +206,16 @@ struct JsnoopBatch {
     int  launch_back_end(uint32_t nimg);        // k_idct_color over the first nimg images (tile size from their CURRENT preview state)
 };
 
+// jsnoop_encode_* (jsnoop_encode.cpp): the encoder's object.  Its arena, its records' page-locked block, its export memory and its stream are those of a private
+// batch on which no decode-side call is ever made: run() fills imgs, one table set (qzz alone), dev.coef and dev.dccum, sets uploaded and last_form = 1, and the
+// export of jsnoop_export.cpp then runs on it unchanged.
+struct JsnoopEncode {
+    JsnoopBatch* b = nullptr;
+    int run(const JsnoopEncodeSpec* spec, const JsnoopEncodeSrc* src, int n);
+    int export_jpeg(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const JsnoopExportProgressive* prog, const int* images, int n);
+    ~JsnoopEncode();
+};
+
 // flags that leave coefficients, planes and DIB of the parallel path reference-exact (bookkeeping differs: status words, warning counter, log)
 #define JS_FLAGS_PIXEL_EXACT (JSNOOP_FLAG_COEF_OVERFLOW | JSNOOP_FLAG_BAD_CODE | JSNOOP_FLAG_RST_MISALIGN)
 // ... of which the parallel side pass can also produce the bookkeeping (the others get theirs from the mirror's side-only pass)

@@ -160,6 +160,9 @@ int  js_launch_export_prog_write(hipStream_t st, const int16_t* coef, const int1
                                  const uint32_t* chunk_base, uint32_t nent, uint32_t nrec, uint32_t tiles, uint32_t chunks, const uint32_t* tabs, const uint16_t* eob, const uint16_t* blk_bits,
                                  const uint64_t* tile_off, uint64_t* itab, uint8_t* ustream, uint32_t* chunk_ff, uint64_t* chunk_off, uint64_t* rec_ff, const uint8_t* hdrs,
                                  const uint32_t* hdr_len, uint64_t* scan_out, uint8_t* out, uint64_t* len);
+// jsnoop_encode_run (jsnoop_encode.hip): k_encode over every unit of the call's records (JsEncRec; unit_base: their prefix table over runs of JS_ENC_RUN MCUs; tabs:
+// the call's two tables and their reciprocals) into the arena and the cumulative DC.  One launch, no scratch.  0, -1 on a launch error.
+int  js_launch_encode(hipStream_t st, const JsEncRec* recs, const uint32_t* unit_base, const JsEncTabs* tabs, uint32_t nrec, uint32_t total_units, int16_t* coef, int16_t* dccum);
 // jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
 // head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
 // the two totals as 64-bit words).  0, -1 on a launch error.

@@ -232,6 +232,15 @@ struct JsExportScanStat { uint32_t freq[JS_PROG_TAB_WORDS]; JsExportOptSlot slot
 // The summaries of the two segmented scans that resolve end-of-band runs (operators and proofs: jsnoop_export_prog_check.h).
 struct JsRunFwd { uint32_t cnt, cut, tail; };    // units behind the last cut (all where cut is 0); a cut lies inside; the last cut was a block with symbols whose band ends in zeros
 struct JsRunBwd { uint32_t lead, open; };        // empty units from the front up to the first stop; no stop inside
+// jsnoop_encode_run (k_encode, jsnoop_encode.hip; arithmetic: jsnoop_encode_check.h): one record per source picture, everything the kernel needs of it resolved on
+// the host, and a prefix table in which picture k owns mcu_ymax * runs units -- a unit is a run of up to JS_ENC_RUN consecutive MCUs of one MCU row, the work
+// of one wave at a time (runs = ceil(mcu_xmax / JS_ENC_RUN); a unit straddles neither a picture nor an MCU row, and an MCU never spans units).  Sample (x, y) of
+// channel c (0, 1, 2 = R, G, B; a grey picture has channel 0 alone) is the byte at base[c] + y * row_step + x * px_step: the host has folded layout, channel
+// order, plane pitch and the bottom-up flag into the three addresses and the signed row step.  sub: 0 = 4:4:4 (and grey), 1 = 4:2:2, 2 = 4:2:0.
+// JsEncTabs: the call's two tables (0 luma, 1 chroma), natural order, and per entry the reciprocal js_enc_recip(q) the quantiser multiplies by.
+#define JS_ENC_RUN 8u                /* public: JSNOOP_ENCODE_RUN */
+struct JsEncRec  { uint64_t base[3]; int64_t row_step; uint64_t coef_off; uint32_t px_step, width, height, ncomp, sub, mcu_xmax, mcu_ymax, runs, bpm, reserved; };
+struct JsEncTabs { uint32_t recip[2][64]; uint16_t q[2][64]; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

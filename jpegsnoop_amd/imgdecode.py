@@ -176,6 +176,8 @@ class JpegBatch:
         self._stream = int(stream) if stream else None   # the caller's hipStream_t, or None: the batch runs on a stream of its own
 
     def close(self):
+        if getattr(self, "_encoder", None) is not None:              # (encode_jpeg's encoder object)
+            self._encoder.close(); self._encoder = None
         if self._h:
             if not getattr(self, "_borrowed", False):
                 self._lib.jsnoop_batch_destroy(self._h)
@@ -974,6 +976,20 @@ class JpegBatch:
         self.sync()
         return out
 
+    def encode_jpeg(self, images=None, size=None, roi=None, filter="bilinear", **encode_options):
+        """The decoded PIXELS of the listed images (None = all) encoded anew on the device: to_torch(layout="HWC") -- with size=(H, W), roi and filter
+        resampled by one jsnoop_batch_pack_resized, the thumbnail sheet -- into scratch tensors, then JpegEncoder.encode on them with encode_options
+        (quality, subsampling, qtables, huffman, restart, progressive, jfif).  A list of bytes, one file per image.  Unlike export_jpeg, which writes
+        the coefficients the batch holds, this quantises again: with the preview mode and the YCC shift applied, at any size and quality.  The encoder
+        object is kept with the batch (the library's current device becomes the batch's)."""
+        if size is None:
+            t = self.to_torch(images, layout="HWC")
+        else:
+            t = self.to_torch(images, layout="HWC", size=size, roi=roi, filter=filter)
+        if getattr(self, "_encoder", None) is None:
+            self._encoder = JpegEncoder(device=self.device())
+        return self._encoder.encode(list(t), **encode_options)
+
     def export_tiff(self, i, path: str, mode: int = 0):
         self._chk(self._lib.jsnoop_batch_export_tiff(self._h, i, path.encode(), mode), "batch_export_tiff")
 
@@ -982,6 +998,189 @@ class JpegBatch:
         """HBM that upload() requests for the images the batch holds now (jsnoop_batch_device_bytes)."""
         return int(self._lib.jsnoop_batch_device_bytes(self._h))
     def pixels(self): return int(self._lib.jsnoop_batch_pixels(self._h))
+
+
+class JpegEncoder:
+    """8-bit pictures in device memory -> JPEG files, transformed, quantised and entropy-coded on the device (jsnoop_encode_* of include/jsnoop_gpu.h;
+    libjpeg's integer arithmetic, value for value).  The object owns its arena, its export memory and -- unless stream is given -- its stream, on `device`
+    (None: the library's current device)."""
+
+    def __init__(self, device=None, stream=None):
+        self._lib = capi.load()
+        if device is not None and self._lib.jsnoop_set_device(int(device)) != 0:
+            raise RuntimeError("jsnoop_set_device failed: " + capi.last_error())
+        self._h = self._lib.jsnoop_encode_create(C.c_void_p(stream) if stream else None)
+        if not self._h:
+            raise RuntimeError("jsnoop_encode_create failed: " + capi.last_error())
+        self._stream = int(stream) if stream else None
+        self._device = None if device is None else int(device)
+
+    def close(self):
+        if self._h:
+            self._lib.jsnoop_encode_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RuntimeError(f"{what} failed: {capi.last_error()}")
+        return rc
+
+    def __len__(self): return self._lib.jsnoop_encode_count(self._h)
+
+    def info(self, i):
+        """Geometry of image i of the last run: the words of JpegBatch.info."""
+        o = (C.c_uint * 16)()
+        self._chk(self._lib.jsnoop_encode_image_info(self._h, i, o), "encode_image_info")
+        keys = "dim_x dim_y img_x img_y mcu_w mcu_h mcu_xmax mcu_ymax blk_xmax blk_ymax scan_bytes flags path ncomp file_len total_blocks".split()
+        return dict(zip(keys, o))
+
+    @staticmethod
+    def _describe(src, bgr, k):
+        """One source -> (capi.EncodeSrc, the object that keeps its memory alive)."""
+        d = capi.EncodeSrc()
+        if isinstance(src, dict):
+            layouts = {"interleaved": capi.ENCODE_INTERLEAVED, "planar": capi.ENCODE_PLANAR}; orders = {"rgb": capi.ENCODE_RGB, "bgr": capi.ENCODE_BGR}
+            unknown = set(src) - {"ptr", "width", "height", "channels", "layout", "order", "pixel_stride", "row_pitch", "plane_pitch", "bottom_up"}
+            if unknown or src.get("layout", "interleaved") not in layouts or src.get("order", "rgb") not in orders:
+                raise ValueError(f"encode: source {k}: a description has ptr, width, height, channels, layout (\"interleaved\" | \"planar\"), order (\"rgb\" | \"bgr\"), "
+                                 f"pixel_stride, row_pitch, plane_pitch, bottom_up; got {sorted(src)}")
+            d.ptr = int(src["ptr"]); d.width = int(src["width"]); d.height = int(src["height"]); d.channels = int(src.get("channels", 3))
+            d.layout = layouts[src.get("layout", "interleaved")]; d.order = orders[src.get("order", "rgb")]
+            d.pixel_stride = int(src.get("pixel_stride", 0)); d.row_pitch = int(src.get("row_pitch", 0)); d.plane_pitch = int(src.get("plane_pitch", 0))
+            d.bottom_up = 1 if src.get("bottom_up", False) else 0
+            return d, src
+        import torch
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or not src.is_cuda or src.dim() not in (2, 3):
+            raise ValueError(f"encode: source {k} must be a uint8 tensor [H, W, 3], [3, H, W] or [H, W] on the device, or a description of device memory")
+        st = src.stride()
+        if src.numel() == 0 or min(st) < 1:
+            raise ValueError(f"encode: source {k}: empty, or strides {st} below 1")
+        d.ptr = src.data_ptr(); d.order = capi.ENCODE_BGR if bgr else capi.ENCODE_RGB
+        if src.dim() == 2:
+            d.height, d.width = src.shape; d.channels = 1; d.pixel_stride = st[1]; d.row_pitch = st[0]
+        elif src.shape[2] == 3:
+            if st[2] != 1:
+                raise ValueError(f"encode: source {k}: the channels of an [H, W, 3] tensor must be adjacent (strides {st})")
+            d.height, d.width = src.shape[:2]; d.channels = 3; d.layout = capi.ENCODE_INTERLEAVED; d.pixel_stride = st[1]; d.row_pitch = st[0]
+        elif src.shape[0] == 3:
+            d.height, d.width = src.shape[1:]; d.channels = 3; d.layout = capi.ENCODE_PLANAR; d.pixel_stride = st[2]; d.row_pitch = st[1]; d.plane_pitch = st[0]
+        else:
+            raise ValueError(f"encode: source {k} has shape {list(src.shape)}: [H, W, 3], [3, H, W] or [H, W]")
+        return d, src
+
+    def run(self, sources, quality=75, subsampling="4:2:0", qtables=None, bgr=False):
+        """jsnoop_encode_run: the listed pictures into the object's arena, one launch, not waited for.  sources: uint8 device tensors [H, W, 3], [3, H, W]
+        (channels R, G, B; B, G, R with bgr) or [H, W] (grey), any strides whose channel / column steps the library accepts; or dicts describing device
+        memory (ptr, width, height, channels, layout, order, pixel_stride, row_pitch, plane_pitch, bottom_up -- JsnoopEncodeSrc).  quality 1..100, or
+        qtables = (luma64, chroma64) in natural order, values 1..255, taken as they are."""
+        sources = list(sources)
+        spec = capi.encode_spec(self._lib, quality, subsampling, qtables)
+        arr = (capi.EncodeSrc * max(len(sources), 1))(); keep = []
+        dev = None
+        for k, s in enumerate(sources):
+            arr[k], alive = self._describe(s, bgr, k); keep.append(alive)
+            if not isinstance(s, dict):
+                dev = s.device if dev is None else dev
+                if s.device != dev or (self._device is not None and s.device.index != self._device):
+                    raise ValueError(f"encode: source {k} is on {s.device}, not on the encoder's device")
+        if dev is not None:
+            import torch
+            cur = torch.cuda.current_stream(dev)                     # whatever filled the tensors was enqueued there
+            if self._stream != cur.cuda_stream:
+                cur.synchronize()
+        self._chk(self._lib.jsnoop_encode_run(self._h, C.byref(spec), arr, len(sources)), "encode_run")
+        self._keep = keep                                            # (until the next run: the launch reads them)
+        return len(sources)
+
+    def coefs(self, i):
+        """Image i of the last run: (arena rows [blocks][64] int16 -- decode order, natural order inside a row, slot 0 zero --, dccum [blocks] int16)."""
+        nb = self.info(i)["total_blocks"]
+        a = np.empty((nb, 64), np.int16); d = np.empty(nb, np.int16)
+        got = self._chk(self._lib.jsnoop_encode_read_coefs(self._h, i, a.ctypes.data_as(C.POINTER(C.c_int16)), d.ctypes.data_as(C.POINTER(C.c_int16)), nb), "encode_read_coefs")
+        assert got == nb
+        return a, d
+
+    def _export(self, images, jfif, huffman, restart, progressive):
+        rst = capi.export_restart(self._lib, restart)
+        prog = capi.export_progressive(self._lib, progressive)
+        coding = capi.export_coding(self._lib, huffman)
+        spec = capi.ExportSpec()
+        self._lib.jsnoop_export_spec_defaults(C.byref(spec))
+        spec.jfif = 1 if jfif else 0
+        idx = list(range(len(self))) if images is None else [int(i) for i in images]
+        ind = (C.c_int * max(len(idx), 1))(*idx)
+        self._chk(self._lib.jsnoop_encode_export(self._h, C.byref(spec), C.byref(coding), C.byref(rst), C.byref(prog), ind, len(idx)), "encode_export")
+        return self.export_results()
+
+    def export_results(self):
+        """The entries of the last export, as JpegBatch.export_results returns them."""
+        out = []
+        for k in range(self._lib.jsnoop_encode_export_count(self._h)):
+            ptr, ln, res, det, img = C.c_void_p(), C.c_uint64(), C.c_int(), C.c_uint32(), C.c_int()
+            self._chk(self._lib.jsnoop_encode_export_file(self._h, k, C.byref(ptr), C.byref(ln), C.byref(res), C.byref(det), C.byref(img)), "encode_export_file")
+            out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
+        return out
+
+    def export_scans(self, k):
+        """Entry k of the last progressive export: one dict per scan, as JpegBatch.export_scans returns them."""
+        out = []
+        for i in range(self._lib.jsnoop_encode_export_scan_count(self._h, int(k))):
+            sc, ri, n, sos, nb = capi.ExportScan(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            self._chk(self._lib.jsnoop_encode_export_scan_info(self._h, int(k), i, C.byref(sc), C.byref(ri), C.byref(n), C.byref(sos), C.byref(nb)), "encode_export_scan_info")
+            out.append(dict(comps=[c for c in range(8) if sc.comps >> c & 1], ss=sc.ss, se=sc.se, ah=sc.ah, al=sc.al, ri=int(ri.value), intervals=int(n.value),
+                            sos_offset=int(sos.value), data_bytes=int(nb.value)))
+        return out
+
+    def export(self, images=None, jfif=True, huffman="annex_k", restart=0, progressive=False):
+        """The images of the last run (None = all; any order, repeats allowed) as files: a list of bytes, None where an image could not be written
+        (export_results() says why).  huffman, restart and progressive are JpegBatch.export_jpeg's."""
+        files = []
+        for k, e in enumerate(self._export(images, jfif, huffman, restart, progressive)):
+            if not e["len"]:
+                files.append(None); continue
+            buf = (C.c_uint8 * e["len"])()
+            if self._lib.jsnoop_encode_read_export(self._h, k, buf, e["len"]) != e["len"]:
+                raise RuntimeError(f"encode_read_export failed: {capi.last_error()}")
+            files.append(bytes(buf))
+        return files
+
+    def encode(self, sources, quality=75, subsampling="4:2:0", qtables=None, huffman="annex_k", restart=0, progressive=False, bgr=False, jfif=True):
+        """run + export: one file (bytes) per source.  No pixel and no coefficient crosses PCIe; the files do."""
+        self.run(sources, quality, subsampling, qtables, bgr)
+        return self.export(None, jfif, huffman, restart, progressive)
+
+    def encode_to_torch(self, sources, quality=75, subsampling="4:2:0", qtables=None, huffman="annex_k", restart=0, progressive=False, bgr=False, jfif=True):
+        """encode, but the files stay on the device: a list with one uint8 tensor per source (None where it could not be written), copied out of the
+        object's memory by jsnoop_encode_export_copy -- they outlive the next export."""
+        import torch
+        self.run(sources, quality, subsampling, qtables, bgr)
+        res = self._export(None, jfif, huffman, restart, progressive)
+        tens = [s for s in sources if isinstance(s, torch.Tensor)]
+        dev = tens[0].device if tens else torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+        sizes = [-(-e["len"] // 16) * 16 for e in res]
+        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        out, off = [], 0
+        for k, (e, sz) in enumerate(zip(res, sizes)):
+            if not e["len"]:
+                out.append(None); continue
+            t = flat[off:off + e["len"]]; off += sz
+            if self._lib.jsnoop_encode_export_copy(self._h, k, t.data_ptr(), e["len"]) != e["len"]:
+                raise RuntimeError(f"encode_export_copy failed: {capi.last_error()}")
+            out.append(t)
+        if out and any(t is not None for t in out):                   # wait for the copies: one byte of the last entry read back is behind all of them on the stream
+            last = max(k for k, t in enumerate(out) if t is not None)
+            one = (C.c_uint8 * res[last]["len"])()
+            self._lib.jsnoop_encode_read_export(self._h, last, one, res[last]["len"])
+        return out
 
 
 class JpegPipeline:
