@@ -786,6 +786,75 @@ int64_t      jsnoop_encode_export_copy(JsnoopEncode*, int k, void* dev_dst, uint
 int          jsnoop_encode_export_scan_count(const JsnoopEncode*, int k);
 int          jsnoop_encode_export_scan_info(const JsnoopEncode*, int k, int scan, JsnoopExportScan* sc, uint32_t* ri, uint64_t* intervals, uint64_t* sos_offset, uint64_t* data_bytes);
 
+/* ---- transform: flip, rotate, transpose, crop and grayscale of a decoded batch without a second quantisation, on the device -----------------------
+ * jpegtran's lossless transforms: the DCT blocks of every listed image are rearranged (and their cells transposed and sign-changed) into a coefficient
+ * arena and a cumulative-DC array of the form a decode leaves, which the export above then writes as files, unchanged.  No cell is interpreted, none is
+ * quantised again.  tests/transform_model.py is the definition, value for value; DESIGN.md section 4.19 has the contract (grayscale, crop, edge, block
+ * map and signs, descriptor).
+ *
+ * A JsnoopTransform owns its arena, its export memory and (unless the caller passes one) its stream; it lives on the device that was current when it
+ * was created.  jsnoop_transform_run transforms n images of `src` (images == NULL: images 0 .. n - 1) in ONE launch on the object's stream, waits for
+ * nothing on the host, and replaces what the object held.  Where the object's stream is not the source batch's, the launch goes behind an event
+ * recorded on the source batch's stream.  The source needs what jsnoop_batch_pack_coefs needs: decoded, and ensure_generic() after a DC-only fast
+ * decode (the call makes it, as the pack does: that decode is waited for).  Baseline and progressive batches are both accepted.  The caller leaves the
+ * source batch's arena alone (no decode, clear, upload or destroy) until the object's stream has passed the run.  What the arena holds when the
+ * kernel runs is what is transformed: an image the parallel path flagged is final only behind jsnoop_batch_sync (a damaged file then arrives as repaired).
+ *
+ * The spec applies to the whole call; per entry, in this order, in source coordinates (the source MCU is mw = 8 Hmax by mh = 8 Vmax):
+ *   grayscale 1  a three-component source keeps component 0 alone: one component, 1 x 1, ceil(W / 8) x ceil(H / 8) blocks, mw = mh = 8 from here on.
+ *   crop 1       jpegtran's rule: the offset goes down to the MCU grid (x0 = crop_x - crop_x % mw), the size grows by what the offset lost and is
+ *                clipped to the picture.  A rectangle that starts outside the picture: JSNOOP_XFORM_EMPTY.
+ *   edge         an op that reverses the source's x axis (FLIP_H, ROT_180, TRANSVERSE, ROT_270) needs the width to be a multiple of mw, one that
+ *                reverses y (FLIP_V, ROT_180, TRANSVERSE, ROT_90) the height a multiple of mh.  JSNOOP_XFORM_EDGE_TRIM cuts the dimension down to whole
+ *                MCUs from the origin (below one MCU: EMPTY); _EDGE_PERFECT makes the entry JSNOOP_XFORM_IMPERFECT instead.
+ * jsnoop_transform_entry: entry k's result word and its image in the object (-1 where the entry is not OK: it has none; the others are written, in the
+ * order of the call).  JSNOOP_XFORM_UNSUPPORTED: a source whose component count is neither 1 nor 3.  The four transposing ops swap width and height,
+ * H and V of every component, and transpose every quantiser table; precision is the source's; no restart interval is recorded.
+ *
+ * jsnoop_transform_image_info, _image_dqt and _read_coefs are jsnoop_batch_image_info, jsnoop_batch_image_dqt and jsnoop_encode_read_coefs on the
+ * object's images; jsnoop_transform_export is jsnoop_batch_export_jpeg_prog on the object's arena, and _export_count, _export_file, _read_export,
+ * _export_copy, _export_scan_count and _export_scan_info are the batch calls of the same name.  The files stay valid until the next export, run or destroy.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, the previous result untouched: a NULL object, batch or spec; n < 0, or an index out of
+ * range; an unknown op or edge; grayscale or crop other than 0 / 1; crop fields set while crop = 0; crop_w or crop_h of 0; non-zero reserved; a
+ * struct_size that is too small or larger than this library's (read like JsnoopPackSpec's); a source that is not decoded; 2^31 or more blocks in one
+ * call.                                                                                                                                        */
+#define JSNOOP_XFORM_NONE         0        /* libjpeg's JXFORM codes */
+#define JSNOOP_XFORM_FLIP_H       1
+#define JSNOOP_XFORM_FLIP_V       2
+#define JSNOOP_XFORM_TRANSPOSE    3
+#define JSNOOP_XFORM_TRANSVERSE   4
+#define JSNOOP_XFORM_ROT_90       5        /* clockwise */
+#define JSNOOP_XFORM_ROT_180      6
+#define JSNOOP_XFORM_ROT_270      7
+#define JSNOOP_XFORM_EDGE_TRIM    0
+#define JSNOOP_XFORM_EDGE_PERFECT 1
+#define JSNOOP_XFORM_OK           0
+#define JSNOOP_XFORM_IMPERFECT    1
+#define JSNOOP_XFORM_EMPTY        2
+#define JSNOOP_XFORM_UNSUPPORTED  3
+#define JSNOOP_TRANSFORM_RUN      8u       /* destination blocks a wave moves at a time (k_transform), for tests that place pictures at its seams */
+typedef struct JsnoopTransform JsnoopTransform;
+typedef struct JsnoopTransformSpec { uint32_t struct_size; int32_t op, edge; uint32_t grayscale, crop, crop_x, crop_y, crop_w, crop_h, reserved; } JsnoopTransformSpec;
+void*        jsnoop_batch_stream(const JsnoopBatch*);                                             /* the hipStream_t the batch enqueues on (its own or the caller's), to create a transform object on it */
+JsnoopTransform* jsnoop_transform_create(void* stream);                                           /* NULL stream: a stream of its own */
+void         jsnoop_transform_destroy(JsnoopTransform*);
+void         jsnoop_transform_spec_defaults(JsnoopTransformSpec* out);                            /* NONE, TRIM, no crop; NULL tolerated */
+int          jsnoop_transform_run(JsnoopTransform*, JsnoopBatch* src, const JsnoopTransformSpec*, const int* images, int n);
+int          jsnoop_transform_entry(const JsnoopTransform*, int k, int* result, int* image);      /* image: index in the object, -1 where none */
+int          jsnoop_transform_entry_count(const JsnoopTransform*);                                /* entries of the last run */
+int          jsnoop_transform_count(const JsnoopTransform*);                                      /* images the object holds */
+int          jsnoop_transform_image_info(const JsnoopTransform*, int i, unsigned* out16);
+int          jsnoop_transform_image_dqt(const JsnoopTransform*, int i, int comp, uint16_t* out64);
+int          jsnoop_transform_read_coefs(JsnoopTransform*, int i, int16_t* coefs, int16_t* dccum, size_t max_blocks);
+int          jsnoop_transform_export(JsnoopTransform*, const JsnoopExportSpec*, const JsnoopExportCoding*, const JsnoopExportRestart*, const JsnoopExportProgressive*, const int* images, int n);
+int          jsnoop_transform_export_count(const JsnoopTransform*);
+int          jsnoop_transform_export_file(const JsnoopTransform*, int k, const void** dev_ptr, uint64_t* len, int* result, uint32_t* detail, int* image);
+int64_t      jsnoop_transform_read_export(JsnoopTransform*, int k, void* host_dst, uint64_t cap);
+int64_t      jsnoop_transform_export_copy(JsnoopTransform*, int k, void* dev_dst, uint64_t cap);
+int          jsnoop_transform_export_scan_count(const JsnoopTransform*, int k);
+int          jsnoop_transform_export_scan_info(const JsnoopTransform*, int k, int scan, JsnoopExportScan* sc, uint32_t* ri, uint64_t* intervals, uint64_t* sos_offset, uint64_t* data_bytes);
+
 /* ---- staging pipeline: the CwindowBuf replacement at batch scale (source/WindowBuf.cpp:351-416 BufLoadWindow, :639-714 Buf) ----
  * `slots` batch slots, each with its own pinned staging area, HBM arenas and stream (fill them through jsnoop_pipeline_slot and
  * the jsnoop_batch_add* calls).  jsnoop_pipeline_run cycles `batches` batches through the slots: while one slot decodes, the next

@@ -7,5 +7,5 @@ file list over all devices.
 """
 from .capi import load, last_error, LIB_PATH  # noqa: F401
 from .imgdecode import CimgDecode, JpegBatch, JpegJob, JobFileResult, JpegPipeline, dib_checksum_numpy, stats_fields, coef_hist_fields  # noqa: F401
-from .imgdecode import Carve, carve_host, JpegEncoder  # noqa: F401
+from .imgdecode import Carve, carve_host, JpegEncoder, JpegTransform  # noqa: F401
 from .shard import partition_lpt, partition_contiguous, reduce_job_stats  # noqa: F401

@@ -264,6 +264,43 @@ def encode_spec(lib, quality=75, subsampling="4:2:0", qtables=None):
     return s
 
 
+XFORM_NONE, XFORM_FLIP_H, XFORM_FLIP_V, XFORM_TRANSPOSE, XFORM_TRANSVERSE, XFORM_ROT_90, XFORM_ROT_180, XFORM_ROT_270 = range(8)      # libjpeg's JXFORM codes; ROT_90 is clockwise
+XFORM_OPS = {"none": XFORM_NONE, "flip_h": XFORM_FLIP_H, "flip_v": XFORM_FLIP_V, "transpose": XFORM_TRANSPOSE, "transverse": XFORM_TRANSVERSE,
+             "rot90": XFORM_ROT_90, "rot180": XFORM_ROT_180, "rot270": XFORM_ROT_270}
+XFORM_EDGE_TRIM, XFORM_EDGE_PERFECT = 0, 1
+XFORM_EDGES = {"trim": XFORM_EDGE_TRIM, "perfect": XFORM_EDGE_PERFECT}
+XFORM_OK, XFORM_IMPERFECT, XFORM_EMPTY, XFORM_UNSUPPORTED = 0, 1, 2, 3
+XFORM_EXIF = {1: XFORM_NONE, 2: XFORM_FLIP_H, 3: XFORM_ROT_180, 4: XFORM_FLIP_V, 5: XFORM_TRANSPOSE, 6: XFORM_ROT_90, 7: XFORM_TRANSVERSE, 8: XFORM_ROT_270}   # EXIF orientation -> the op that sets it upright
+TRANSFORM_RUN = 8       # JSNOOP_TRANSFORM_RUN of include/jsnoop_gpu.h: destination blocks a wave moves at a time
+
+
+class TransformSpec(C.Structure):
+    """JsnoopTransformSpec of include/jsnoop_gpu.h: op, edge mode, grayscale and crop of one jsnoop_transform_run."""
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_int32), ("edge", C.c_int32), ("grayscale", C.c_uint32), ("crop", C.c_uint32), ("crop_x", C.c_uint32),
+                ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def transform_spec(lib, op="none", edge="trim", grayscale=False, crop=None):
+    """The JsnoopTransformSpec of op (a name of XFORM_OPS or a JXFORM code), edge ("trim" | "perfect" or 0 | 1), grayscale and crop = (x, y, w, h) | None.
+    Numbers are handed to the library as given: it refuses what is out of range."""
+    s = TransformSpec()
+    lib.jsnoop_transform_spec_defaults(C.byref(s))
+    if isinstance(op, str) and op not in XFORM_OPS:
+        raise ValueError("op must be one of %s or a JXFORM code, not %r" % (", ".join(XFORM_OPS), op))
+    if isinstance(edge, str) and edge not in XFORM_EDGES:
+        raise ValueError('edge must be "trim" or "perfect", not %r' % (edge,))
+    s.op = XFORM_OPS[op] if isinstance(op, str) else int(op)
+    s.edge = XFORM_EDGES[edge] if isinstance(edge, str) else int(edge)
+    s.grayscale = int(grayscale)
+    if crop is not None:
+        try:
+            x, y, w, h = (int(v) for v in crop)
+        except (TypeError, ValueError):
+            raise ValueError("crop must be (x, y, w, h)") from None
+        s.crop = 1; s.crop_x, s.crop_y, s.crop_w, s.crop_h = x, y, w, h
+    return s
+
+
 CARVE_OK, CARVE_NO_SOS, CARVE_NO_EOI, CARVE_STOPPED, CARVE_LIMIT = 0, 1, 2, 3, 4
 CARVE_NOT_A_MARKER, CARVE_RST_OUTSIDE_SCAN, CARVE_BAD_LENGTH, CARVE_UNKNOWN_MARKER = 1, 2, 3, 4
 CARVE_SEEN_SOI_AGAIN, CARVE_SEEN_DQT, CARVE_SEEN_DHT, CARVE_SEEN_DRI, CARVE_SEEN_AVI1 = 1, 2, 4, 8, 16
@@ -464,6 +501,24 @@ SIGNATURES = {
     "jsnoop_encode_export_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
     "jsnoop_encode_export_scan_count": (_i, [_p, _i]),
     "jsnoop_encode_export_scan_info": (_i, [_p, _i, _i, C.POINTER(ExportScan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jsnoop_batch_stream": (_p, [_p]),
+    "jsnoop_transform_create": (_p, [_p]),
+    "jsnoop_transform_destroy": (None, [_p]),
+    "jsnoop_transform_spec_defaults": (None, [C.POINTER(TransformSpec)]),
+    "jsnoop_transform_run": (_i, [_p, _p, C.POINTER(TransformSpec), _PI, _i]),
+    "jsnoop_transform_entry": (_i, [_p, _i, _PI, _PI]),
+    "jsnoop_transform_entry_count": (_i, [_p]),
+    "jsnoop_transform_count": (_i, [_p]),
+    "jsnoop_transform_image_info": (_i, [_p, _i, _PU]),
+    "jsnoop_transform_image_dqt": (_i, [_p, _i, _i, C.POINTER(C.c_uint16)]),
+    "jsnoop_transform_read_coefs": (_i, [_p, _i, C.POINTER(C.c_int16), C.POINTER(C.c_int16), _sz]),
+    "jsnoop_transform_export": (_i, [_p, C.POINTER(ExportSpec), C.POINTER(ExportCoding), C.POINTER(ExportRestart), C.POINTER(ExportProgressive), _PI, _i]),
+    "jsnoop_transform_export_count": (_i, [_p]),
+    "jsnoop_transform_export_file": (_i, [_p, _i, C.POINTER(_p), C.POINTER(C.c_uint64), _PI, C.POINTER(C.c_uint32), _PI]),
+    "jsnoop_transform_read_export": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_transform_export_copy": (C.c_int64, [_p, _i, _p, C.c_uint64]),
+    "jsnoop_transform_export_scan_count": (_i, [_p, _i]),
+    "jsnoop_transform_export_scan_info": (_i, [_p, _i, _i, C.POINTER(ExportScan), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jsnoop_partition_lpt": (_i, [C.POINTER(C.c_uint64), _i, _i, _PI]),
     "jsnoop_job_create": (_p, [_PI, _i]),
     "jsnoop_job_destroy": (None, [_p]),

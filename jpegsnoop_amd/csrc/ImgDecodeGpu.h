@@ -307,6 +307,33 @@ public:
         jsnoop_encode_destroy(e);
         return ok;
     }
+    // jpegtran's lossless transforms of the decoded batch: the listed files (empty = all) flipped, rotated, transposed, cropped or made grey on the device without
+    // a second quantisation and written as files (jsnoop_transform_run + jsnoop_transform_export on a transform object of its own, on the batch's stream;
+    // jsnoop_transform_spec_defaults fills a spec).  results[k]: JSNOOP_XFORM_* of entry k; out[k]: its file, empty where the entry is not OK or could not be
+    // written.  pCoding / pRestart / pProg: NULL = Annex K tables, no restart markers, baseline.  After DoBatchProcess.
+    bool     TransformJpeg(const JsnoopTransformSpec& spec, const std::vector<int>& files, std::vector<int>& results, std::vector<std::vector<uint8_t>>& out, bool bJfif = true,
+                           const JsnoopExportCoding* pCoding = nullptr, const JsnoopExportRestart* pRestart = nullptr, const JsnoopExportProgressive* pProg = nullptr)
+    {
+        results.clear(); out.clear();
+        JsnoopTransform* t = jsnoop_transform_create(jsnoop_batch_stream(m_b));
+        if (!t) return false;
+        const int* p = files.empty() ? nullptr : files.data(); const int n = files.empty() ? jsnoop_batch_count(m_b) : (int)files.size();
+        JsnoopExportSpec ex; jsnoop_export_spec_defaults(&ex); ex.jfif = bJfif ? 1 : 0;
+        bool ok = jsnoop_transform_run(t, m_b, &spec, p, n) == 0;
+        if (ok && jsnoop_transform_count(t)) ok = jsnoop_transform_export(t, &ex, pCoding, pRestart, pProg, nullptr, jsnoop_transform_count(t)) == 0;
+        for (int k = 0; ok && k < n; k++) {
+            int nResult = 0, nImage = -1; uint64_t nLen = 0;
+            ok = jsnoop_transform_entry(t, k, &nResult, &nImage) == 0;
+            results.push_back(nResult); out.emplace_back();
+            if (ok && nImage >= 0) {
+                ok = jsnoop_transform_export_file(t, nImage, nullptr, &nLen, nullptr, nullptr, nullptr) == 0;
+                out.back().resize((size_t)nLen);
+                if (ok && nLen) ok = jsnoop_transform_read_export(t, nImage, out.back().data(), nLen) == (int64_t)nLen;
+            }
+        }
+        jsnoop_transform_destroy(t);
+        return ok;
+    }
     // BatchExportJpeg with a restart interval per file (jsnoop_batch_export_jpeg_rst): nMode JSNOOP_RESTART_*, nInterval in MCUs or MCU rows; BatchExportRestart: what entry k got
     bool     BatchExportJpegRestart(const std::vector<int>& files, bool bJfif, bool bOptimal, int nMode, unsigned nInterval)
     { JsnoopExportSpec spec; jsnoop_export_spec_defaults(&spec); spec.jfif = bJfif ? 1 : 0;

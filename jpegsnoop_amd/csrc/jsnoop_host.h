@@ -216,6 +216,18 @@ struct JsnoopEncode {
     ~JsnoopEncode();
 };
 
+// jsnoop_transform_* (jsnoop_transform.cpp): the transform's object, built like the encoder's.  Its arena, its records' page-locked block, its export memory and
+// its stream are those of a private batch on which no decode-side call is ever made: run() fills imgs, tables (qzz alone), dev.coef and dev.dccum from a decoded
+// source batch, sets uploaded and last_form = 1, and the export of jsnoop_export.cpp then runs on it unchanged.  results / image_of: the entries of the last run.
+struct JsnoopTransform {
+    JsnoopBatch* b = nullptr;
+    std::vector<int> results, image_of;
+    hipEvent_t ev_src = nullptr;                 // recorded on the source batch's stream where it is not the object's; the launch waits for it
+    int run(JsnoopBatch* src, const JsnoopTransformSpec* spec, const int* images, int n);
+    int export_jpeg(const JsnoopExportSpec* spec, const JsnoopExportCoding* coding, const JsnoopExportRestart* restart, const JsnoopExportProgressive* prog, const int* images, int n);
+    ~JsnoopTransform();
+};
+
 // flags that leave coefficients, planes and DIB of the parallel path reference-exact (bookkeeping differs: status words, warning counter, log)
 #define JS_FLAGS_PIXEL_EXACT (JSNOOP_FLAG_COEF_OVERFLOW | JSNOOP_FLAG_BAD_CODE | JSNOOP_FLAG_RST_MISALIGN)
 // ... of which the parallel side pass can also produce the bookkeeping (the others get theirs from the mirror's side-only pass)

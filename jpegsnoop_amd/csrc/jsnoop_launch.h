@@ -163,6 +163,11 @@ int  js_launch_export_prog_write(hipStream_t st, const int16_t* coef, const int1
 // jsnoop_encode_run (jsnoop_encode.hip): k_encode over every unit of the call's records (JsEncRec; unit_base: their prefix table over runs of JS_ENC_RUN MCUs; tabs:
 // the call's two tables and their reciprocals) into the arena and the cumulative DC.  One launch, no scratch.  0, -1 on a launch error.
 int  js_launch_encode(hipStream_t st, const JsEncRec* recs, const uint32_t* unit_base, const JsEncTabs* tabs, uint32_t nrec, uint32_t total_units, int16_t* coef, int16_t* dccum);
+// jsnoop_transform_run (jsnoop_transform.hip): k_transform over every unit of the call's records (JsXfRec; unit_base: their prefix table over runs of JS_XF_RUN
+// destination blocks; flags: what the call's op comes to, JS_XF_*) from the source batch's arena and cumulative DC into the object's.  One launch, no scratch.
+// 0, -1 on a launch error.
+int  js_launch_transform(hipStream_t st, const JsXfRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units, uint32_t flags,
+                         const int16_t* src_coef, const int16_t* src_dccum, int16_t* coef, int16_t* dccum);
 // jsnoop_carve_run (jsnoop_carve.hip), first phase: k_carve_count over every tile of the blob, then k_carve_scan.  base: the 16-byte boundary at or below the blob,
 // head: the bytes between the two, n: the blob's length; counts: 4 * tiles + 4 words (per tile terminators and candidates, then their exclusive prefix sums, then
 // the two totals as 64-bit words).  0, -1 on a launch error.

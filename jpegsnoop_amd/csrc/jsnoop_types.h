@@ -241,6 +241,22 @@ struct JsRunBwd { uint32_t lead, open; };        // empty units from the front u
 #define JS_ENC_RUN 8u                /* public: JSNOOP_ENCODE_RUN */
 struct JsEncRec  { uint64_t base[3]; int64_t row_step; uint64_t coef_off; uint32_t px_step, width, height, ncomp, sub, mcu_xmax, mcu_ymax, runs, bpm, reserved; };
 struct JsEncTabs { uint32_t recip[2][64]; uint16_t q[2][64]; };
+// jsnoop_transform_run (k_transform, jsnoop_transform.hip; geometry, block map and plan: jsnoop_transform_check.h): one record per entry that is written --
+// everything the kernel needs of it resolved on the host -- and a prefix table in which entry k owns ceil(nblk / JS_XF_RUN) units: a unit is a run of up to
+// JS_XF_RUN consecutive DESTINATION blocks (decode order of the new geometry), the work of one wave at a time.  An op maps MCUs onto MCUs: the region is rw x rh
+// MCUs of the layout the entry works in (the source's; 8 x 8 single blocks under grayscale), its origin (ox, oy) counted in such MCUs, and block kb of a
+// destination MCU is block tab[kb] of the source MCU it comes from.  Under grayscale a working MCU is one of the gsh x gsv blocks component 0 has in a source MCU
+// (gsh = gsv = 1 otherwise).  m_*: the divisions by the destination's blocks per MCU and MCUs per row and by gsh and gsv as multiply-high words (js_xf_magic).
+// What the op comes to is call-wide (JS_XF_* flag bits).
+#define JS_XF_RUN 8u                 /* public: JSNOOP_TRANSFORM_RUN */
+#define JS_XF_T     1u               /* the 8 x 8 cells and the block grid are transposed */
+#define JS_XF_REVX  2u               /* the source's x axis is reversed */
+#define JS_XF_REVY  4u               /* the source's y axis is reversed */
+#define JS_XF_NEGU  8u               /* destination cells of odd u change sign */
+#define JS_XF_NEGV 16u               /* destination cells of odd v change sign */
+struct JsXfDiv  { uint32_t mul, shift; };                        // mul 0: the divisor is 1
+struct JsXfRec  { uint64_t src_off, dst_off; uint32_t nblk, s_mcu_x, s_bpm, d_mcu_x, d_bpm, rw, rh, ox, oy, gsh, gsv, reserved; JsXfDiv m_bpm, m_mcu_x, m_gsh, m_gsv;
+                  uint8_t tab[JS_MAX_BLK_PER_MCU]; };
 // zig-zag position of natural index k: the inverse of JS_ZIGZAG_NATURAL below
 #define JS_ZIGZAG_POSITION { 0, 1, 5, 6,14,15,27,28,  2, 4, 7,13,16,26,29,42,  3, 8,12,17,25,30,41,43,  9,11,18,24,31,40,44,53, \
                             10,19,23,32,39,45,52,54, 20,22,33,38,46,51,55,60, 21,34,37,47,50,56,59,61, 35,36,48,49,57,58,62,63 }

@@ -990,6 +990,18 @@ class JpegBatch:
             self._encoder = JpegEncoder(device=self.device())
         return self._encoder.encode(list(t), **encode_options)
 
+    def transform(self, op, images=None, crop=None, edge="trim", grayscale=False):
+        """The listed images (None = all) flipped, rotated, transposed, cropped or made grey WITHOUT a second quantisation: a JpegTransform on the batch's
+        stream, run once (JpegTransform.run has the arguments; .entries() says what became of each image, .export() writes the files, .coefs(i) reads the
+        arena).  The caller closes it.  Nothing is waited for: the batch must not be decoded, cleared or closed until the transform's stream has passed the run
+        (any read through the object waits for it)."""
+        t = JpegTransform(device=self.device(), stream=self._lib.jsnoop_batch_stream(self._h))
+        try:
+            t.run(self, op, images, crop, edge, grayscale)
+        except Exception:
+            t.close(); raise
+        return t
+
     def export_tiff(self, i, path: str, mode: int = 0):
         self._chk(self._lib.jsnoop_batch_export_tiff(self._h, i, path.encode(), mode), "batch_export_tiff")
 
@@ -1180,6 +1192,154 @@ class JpegEncoder:
             last = max(k for k, t in enumerate(out) if t is not None)
             one = (C.c_uint8 * res[last]["len"])()
             self._lib.jsnoop_encode_read_export(self._h, last, one, res[last]["len"])
+        return out
+
+
+class JpegTransform:
+    """jpegtran's lossless transforms of a decoded batch on the device: flip, rotate, transpose, transverse, crop and grayscale rearrange the DCT blocks
+    the batch holds into an arena of this object's, without a second quantisation, and the export writes that arena as files (jsnoop_transform_* of
+    include/jsnoop_gpu.h).  The object owns its arena, its export memory and -- unless stream is given -- its stream, on `device` (None:
+    the library's current device).  JpegBatch.transform makes one on the batch's stream and runs it."""
+
+    def __init__(self, device=None, stream=None):
+        self._lib = capi.load()
+        if device is not None and self._lib.jsnoop_set_device(int(device)) != 0:
+            raise RuntimeError("jsnoop_set_device failed: " + capi.last_error())
+        self._h = self._lib.jsnoop_transform_create(C.c_void_p(stream) if stream else None)
+        if not self._h:
+            raise RuntimeError("jsnoop_transform_create failed: " + capi.last_error())
+        self._stream = int(stream) if stream else None
+        self._device = None if device is None else int(device)
+
+    def close(self):
+        if self._h:
+            self._lib.jsnoop_transform_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise RuntimeError(f"{what} failed: {capi.last_error()}")
+        return rc
+
+    def __len__(self): return self._lib.jsnoop_transform_count(self._h)
+
+    def run(self, batch, op="none", images=None, crop=None, edge="trim", grayscale=False):
+        """jsnoop_transform_run: the listed images of `batch` (a decoded JpegBatch; None = all, any order, repeats allowed) into the object's arena, one
+        launch, not waited for.  op: "none" | "flip_h" | "flip_v" | "transpose" | "transverse" | "rot90" (clockwise) | "rot180" | "rot270" or a JXFORM
+        code (capi.XFORM_EXIF maps an EXIF orientation to the op that sets the picture upright); crop = (x, y, w, h) by jpegtran's rule; edge "trim"
+        cuts a reversed dimension down to whole MCUs, "perfect" refuses such an entry (IMPERFECT); grayscale keeps component 0 alone.  Returns
+        entries().  The batch's arena must stay as it is until the object's stream has passed the run; call batch.sync() first where damaged files
+        should be transformed as repaired."""
+        spec = capi.transform_spec(self._lib, op, edge, grayscale, crop)
+        idx = list(range(len(batch))) if images is None else [int(i) for i in images]
+        ind = (C.c_int * max(len(idx), 1))(*idx)
+        self._chk(self._lib.jsnoop_transform_run(self._h, batch._h, C.byref(spec), ind, len(idx)), "transform_run")
+        return self.entries()
+
+    def entries(self):
+        """The entries of the last run: dict(result, image) each -- result capi.XFORM_OK / _IMPERFECT / _EMPTY / _UNSUPPORTED, image the entry's index in
+        this object or -1 where it has none."""
+        out = []
+        for k in range(self._lib.jsnoop_transform_entry_count(self._h)):
+            res, img = C.c_int(), C.c_int()
+            self._chk(self._lib.jsnoop_transform_entry(self._h, k, C.byref(res), C.byref(img)), "transform_entry")
+            out.append(dict(result=res.value, image=img.value))
+        return out
+
+    def info(self, i):
+        """Geometry of image i of the last run: the words of JpegBatch.info."""
+        o = (C.c_uint * 16)()
+        self._chk(self._lib.jsnoop_transform_image_info(self._h, i, o), "transform_image_info")
+        keys = "dim_x dim_y img_x img_y mcu_w mcu_h mcu_xmax mcu_ymax blk_xmax blk_ymax scan_bytes flags path ncomp file_len total_blocks".split()
+        return dict(zip(keys, o))
+
+    def dqt(self, i, comp):
+        """The 64 multipliers of component comp of image i, natural order (transposed where the op transposes)."""
+        q = (C.c_uint16 * 64)()
+        self._chk(self._lib.jsnoop_transform_image_dqt(self._h, i, comp, q), "transform_image_dqt")
+        return list(q)
+
+    def coefs(self, i):
+        """Image i of the last run: (arena rows [blocks][64] int16 -- decode order of the new geometry, natural order inside a row --, dccum [blocks] int16)."""
+        nb = self.info(i)["total_blocks"]
+        a = np.empty((nb, 64), np.int16); d = np.empty(nb, np.int16)
+        got = self._chk(self._lib.jsnoop_transform_read_coefs(self._h, i, a.ctypes.data_as(C.POINTER(C.c_int16)), d.ctypes.data_as(C.POINTER(C.c_int16)), nb), "transform_read_coefs")
+        assert got == nb
+        return a, d
+
+    def _export(self, images, jfif, huffman, restart, progressive):
+        rst = capi.export_restart(self._lib, restart)
+        prog = capi.export_progressive(self._lib, progressive)
+        coding = capi.export_coding(self._lib, huffman)
+        spec = capi.ExportSpec()
+        self._lib.jsnoop_export_spec_defaults(C.byref(spec))
+        spec.jfif = 1 if jfif else 0
+        idx = list(range(len(self))) if images is None else [int(i) for i in images]
+        ind = (C.c_int * max(len(idx), 1))(*idx)
+        self._chk(self._lib.jsnoop_transform_export(self._h, C.byref(spec), C.byref(coding), C.byref(rst), C.byref(prog), ind, len(idx)), "transform_export")
+        return self.export_results()
+
+    def export_results(self):
+        """The entries of the last export, as JpegBatch.export_results returns them."""
+        out = []
+        for k in range(self._lib.jsnoop_transform_export_count(self._h)):
+            ptr, ln, res, det, img = C.c_void_p(), C.c_uint64(), C.c_int(), C.c_uint32(), C.c_int()
+            self._chk(self._lib.jsnoop_transform_export_file(self._h, k, C.byref(ptr), C.byref(ln), C.byref(res), C.byref(det), C.byref(img)), "transform_export_file")
+            out.append(dict(image=img.value, result=res.value, detail=det.value, len=int(ln.value), ptr=int(ptr.value or 0)))
+        return out
+
+    def export_scans(self, k):
+        """Entry k of the last progressive export: one dict per scan, as JpegBatch.export_scans returns them."""
+        out = []
+        for i in range(self._lib.jsnoop_transform_export_scan_count(self._h, int(k))):
+            sc, ri, n, sos, nb = capi.ExportScan(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            self._chk(self._lib.jsnoop_transform_export_scan_info(self._h, int(k), i, C.byref(sc), C.byref(ri), C.byref(n), C.byref(sos), C.byref(nb)), "transform_export_scan_info")
+            out.append(dict(comps=[c for c in range(8) if sc.comps >> c & 1], ss=sc.ss, se=sc.se, ah=sc.ah, al=sc.al, ri=int(ri.value), intervals=int(n.value),
+                            sos_offset=int(sos.value), data_bytes=int(nb.value)))
+        return out
+
+    def export(self, images=None, jfif=True, huffman="annex_k", restart=0, progressive=False):
+        """The images of the last run (None = all; any order, repeats allowed) as files: a list of bytes, None where an image could not be written
+        (export_results() says why).  huffman, restart and progressive are JpegBatch.export_jpeg's; "source" finds no restart interval."""
+        files = []
+        for k, e in enumerate(self._export(images, jfif, huffman, restart, progressive)):
+            if not e["len"]:
+                files.append(None); continue
+            buf = (C.c_uint8 * e["len"])()
+            if self._lib.jsnoop_transform_read_export(self._h, k, buf, e["len"]) != e["len"]:
+                raise RuntimeError(f"transform_read_export failed: {capi.last_error()}")
+            files.append(bytes(buf))
+        return files
+
+    def export_to_torch(self, images=None, jfif=True, huffman="annex_k", restart=0, progressive=False, device=None):
+        """export, but the files stay on the device: a list with one uint8 tensor per entry (None where it could not be written), copied out of the
+        object's memory by jsnoop_transform_export_copy -- they outlive the next export."""
+        import torch
+        res = self._export(images, jfif, huffman, restart, progressive)
+        dev = torch.device("cuda", device if device is not None else (self._device if self._device is not None else torch.cuda.current_device()))
+        sizes = [-(-e["len"] // 16) * 16 for e in res]
+        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        if self._stream != cur.cuda_stream:
+            cur.synchronize()
+        out, off = [], 0
+        for k, (e, sz) in enumerate(zip(res, sizes)):
+            if not e["len"]:
+                out.append(None); continue
+            t = flat[off:off + e["len"]]; off += sz
+            if self._lib.jsnoop_transform_export_copy(self._h, k, t.data_ptr(), e["len"]) != e["len"]:
+                raise RuntimeError(f"transform_export_copy failed: {capi.last_error()}")
+            out.append(t)
+        if out and any(t is not None for t in out):                   # wait for the copies: the last entry read back is behind all of them on the stream
+            last = max(k for k, t in enumerate(out) if t is not None)
+            one = (C.c_uint8 * res[last]["len"])()
+            self._lib.jsnoop_transform_read_export(self._h, last, one, res[last]["len"])
         return out
 
 
