@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import batch_stats_cases as BC
+import deal_cases as D
 import stats_cases as SC
 import stats_model as SM
 from stats_cases_util import OPTION_SETS, explain, run_passes
@@ -264,3 +265,60 @@ def test_job_file_result_inside_the_callback(harness, oracle, world, full):
         assert seen[k][0].shape == (1, WORDS) and np.array_equal(seen[k][0][0], rows[i]) and np.array_equal(seen[k][1][0], tot[i]), world[i].case.name
     assert np.array_equal(seen[3][0][0], seen[3][2]) and int(seen[3][0][0][36]) == 96 * 64, "a progressive image: the per-image door's words"
     assert np.array_equal(seen[3][0][0], run_passes(harness, oracle, twin, "histo")["words"][0]), "... and the oracle's for its baseline twin"
+
+
+# ------------------------------------------------------------------------------------------------------------------ the deal: a wave walks several units and records
+def _deal_case(pic, k, long_one):
+    """A picture of tests/deal_cases.py as a stats_cases.Case: every block a level of its own; range events in every second short picture (a block of
+    one component) and in the LAST block of a long one -- its last picture rows, which a wave reaches at the end of a long walk through the record."""
+    layout, w, h = pic
+    fr = SC.frame_of(layout, w, h); rng = np.random.default_rng(7000 + k); g = SC._grids(fr)
+    for c in range(fr.ncomp):
+        g[c][:] = rng.integers(-1000, 1001, g[c].shape)
+    if long_one or k % 2 == 0:
+        c = k % fr.ncomp
+        g[c][-1, -1] = SC.OVER if k % 4 < 2 else SC.UNDER
+    return SC.Case("deal_%s_%dx%d" % pic, "D", layout, w, h, g)
+
+
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(harness, oracle, gpu, capsys):
+    """The catalogue above is a few hundred units: a share of four, a unit a wave, one flush at the end.  Here both forms of k_stats_batch get a call sized
+    from the device (tests/deal_cases.py, proven on the CPU by tests/test_deal_cases.py): a share of twelve units and more, a wave that carries its
+    accumulators and its LDS histogram over several units of one picture, flushes them into that picture's row when the walk leaves it and goes on into
+    the next picture, shares that start inside pictures and on their first row.  A record is at least eight picture rows -- two steps of a wave --, so no
+    step passes over a record here; three pictures in one share is what can be had.  A dozen distinct pictures listed many times; every row, every
+    total and (through k_stats_order's budget, which reads rowcnt) every event's picture row against the oracle's words."""
+    import torch
+    import jpegsnoop_amd as J
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lists = {form: D.stats_records(cus, form) for form in ("hist", "plain")}
+    for form, recs in lists.items():
+        c = D.census_of("stats", form, recs, cus)
+        with capsys.disabled():
+            print("\nk_stats_batch<%s>, %d compute units: %s" % (form, cus, D.summary(c)))
+        assert D.missing(c, D.KERNELS["stats"]["waves"], **D.conditions("stats", form)) == [], D.summary(c)
+    distinct = sorted({r.pic for recs in lists.values() for r in recs})
+    longs = {r.pic for recs in lists.values() for r in recs if r.units >= 40 * D.STATS_STEP}
+    answers = [Answer(harness, oracle, _deal_case(p, k, p in longs)) for k, p in enumerate(distinct)]
+    for p, a in zip(distinct, answers):
+        assert D.stats_sizes(p) == ([BC.UNIT] * (-(-a.case.img_x // BC.UNIT) - 1) + [a.case.img_x - BC.UNIT * (-(-a.case.img_x // BC.UNIT) - 1)]) * a.case.img_y, p
+        ev = sum(a.totals("histo"))
+        assert (ev > 0) == (p in longs or distinct.index(p) % 2 == 0) and (p not in longs or ev > 10), (p, ev)
+    b = _decoded(J, [a.case.file for a in answers])
+    try:
+        errs = []
+        for form, recs in lists.items():
+            picks = [distinct.index(r.pic) for r in recs]
+            if form == "hist":
+                rows, tot = b.stats_to_torch(images=picks, totals=True)
+            else:
+                rows, tot = b.stats_to_torch(images=picks, histo_en=False, totals=True)
+            rows = rows.cpu().numpy().view(np.uint32); tot = tot.cpu().numpy()
+            assert rows.shape == (len(recs), WORDS) and tot.shape == (len(recs), 6)
+            _compare(answers, picks, rows, "histo" if form == "hist" else "clip", errs, form)
+            want = {i: answers[i].totals("histo") for i in set(picks)}
+            errs += ["%s row %d (%s): totals %s, the model's events by kind %s" % (form, k, distinct[i], tot[k].tolist(), want[i]) for k, i in enumerate(picks) if tot[k].tolist() != want[i]]
+        assert not errs, "%d findings\n%s" % (len(errs), "\n".join(errs[:25]))
+    finally:
+        b.close()
+

@@ -13,6 +13,7 @@ import pytest
 import coef_hist_cases as HC
 import coef_hist_model as HM
 import coef_model as M
+import deal_cases as D
 import fuzz_util as F
 
 pytestmark = pytest.mark.gpu
@@ -304,6 +305,43 @@ def test_a_destination_over_three_shares_and_a_share_over_three_destinations(har
     try:
         for form in ((127, True, False), (16, False, True), (1, True, False)):
             pack_and_check(J, torch, b, views, pairs, form, what="deal")
+    finally:
+        b.close()
+
+
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_destinations(harness, oracles, capsys):
+    """The test above has shares of CH_WAVES units: a wave takes one unit of a destination, if any.  Here the list is sized from the device
+    (tests/deal_cases.py, proven on the CPU by tests/test_deal_cases.py): a share of 24 units and more.  Destinations of 3 shares and more lie in the
+    middle of the list -- whole shares inside one destination, every wave with three units and its minima and maxima carried from unit to unit --, a
+    wave takes two and more units of a destination before the share flushes and moves on to the next, one share holds up to a share's length of
+    one-unit destinations, flushed one after the other through the same histogram, and shares start inside destinations and on their first unit.
+    k_coef_hist walks a share destination by destination: `k++` once a destination, no step passes over one.  A dozen distinct (file, component) pairs
+    listed a few hundred times; R = 16 and R = 1, and R = 127 (65 KB a row) over the same list; the whole arena of every call against the model."""
+    import jpegsnoop_amd as J
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    recs = D.coef_hist_records(cus)
+    c = D.census_of("coef_hist", "any", recs, cus)
+    with capsys.disabled():
+        print("\nk_coef_hist, %d compute units: %s; some workgroup's waves take %d units each" % (cus, D.summary(c), c.best_full))
+    assert D.missing(c, D.KERNELS["coef_hist"]["waves"], **D.conditions("coef_hist", "any")) == [], D.summary(c)
+    assert len(recs) < 500
+    images = sorted({r.pic[:3] for r in recs})
+    files = [harness.synth_jpeg(width=w, height=h, quality=(95, 85)[k % 2], restart_interval=(0, 5)[k % 2], seed=3300 + k, **LAYOUTS[l]) for k, (l, w, h) in enumerate(images)]
+    views = [HC.OracleView(harness, oracles, f) for f in files]
+    pairs = [(images.index(r.pic[:3]), r.pic[3]) for r in recs]
+    U = J.capi.COEF_HIST_UNIT
+    for r, (i, comp) in zip(recs, pairs):                             # the units the census counted are the units of the call
+        n = int(np.prod(views[i].geo.grid(comp)))
+        assert r.sizes == [U] * (n // U) + ([n % U] if n % U else []), r.pic
+    k_long = [k for k, r in enumerate(recs) if r.units >= 3 * c.S]
+    assert any(len(recs) // 4 < k < 3 * len(recs) // 4 for k in k_long), "a destination of three shares in the middle of the list"
+    for R in (16, 1, 127):
+        assert c.S == J.capi.coef_hist_share(c.total, cus, R)
+    b = decoded_batch(J, files)
+    try:
+        for form in ((16, True, False), (1, True, True), (127, False, True)):
+            pack_and_check(J, torch, b, views, pairs, form, what="deal", calls=1 if form[0] == 127 else 2)
     finally:
         b.close()
 

@@ -4,8 +4,8 @@ of a decoded batch as one tensor per component in caller-owned device memory.
 Every comparison is exact against tests/coef_model.py fed with the ORACLE's numbers (tests/test_coef_model.py pins them on the CPU): the blocks
 are oracle_coefs() of a Full-IDCT decode, the cumulative DC of a block is the top-left sample of its area in the int16 plane of the oracle's
 decode_ac = 0 decode.  Raw calls write into an arena of 0xA5 bytes -- a guard band in front of, behind and between the destinations and in every
-pitch gap -- and the whole arena is compared with what the model predicts: a stray write anywhere shows.  Images are tiny; the one larger batch is
-there for the deal of work over many workgroups.
+pitch gap -- and the whole arena is compared with what the model predicts: a stray write anywhere shows.  Images are tiny; the one larger batch
+spreads the work over many workgroups, and the call behind it is sized so that a wave walks several units and destinations (tests/deal_cases.py).
 
 The damaged files are tests/fuzz_util.py's flipped-bit variants (mode 0) of bases 0 and 1 with seeds 81 and 77: on the CPU the oracle's
 decode_ac = 0 pass was checked to take the same path through them as its Full-IDCT pass (same status words, same slot 0 in every block)."""
@@ -16,6 +16,7 @@ import pytest
 
 import coef_model as M
 import dc_scan_cases as DC
+import deal_cases as D
 import fuzz_util as F
 import prog_cases as PC
 
@@ -310,6 +311,9 @@ def test_refusals_launch_nothing_write_nothing_and_name_their_reason(seam, harne
 
 # ------------------------------------------------------------------------------------------------ the deal, two streams, DC-only
 def test_64_images_of_333x217_dealt_over_many_workgroups(harness, oracles):
+    """About 4500 units over more than a thousand workgroups.  On a device of 256 compute units that is still below CF_WAVES * 5 * 256 units: a
+    workgroup's share is four units and a wave takes ONE -- the shares fall on every phase of the destinations, but no wave walks from one unit to the
+    next.  That is test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records below."""
     import jpegsnoop_amd as J
     import torch
     files = [harness.synth_jpeg(width=333, height=217, quality=80, restart_interval=(0, 3)[k % 2], seed=1200 + k, **LAYOUTS[(2, 1, 0, 3)[k % 4]]) for k in range(4)]
@@ -323,6 +327,37 @@ def test_64_images_of_333x217_dealt_over_many_workgroups(harness, oracles):
         dests = all_components(tr)
         for form in (("blocks", "int16", False), ("freq", "int16", False), ("freq", "float32", True), ("blocks", "int16", True)):
             pack_and_check(J, torch, b, tr, dests, form, what="64 images")
+    finally:
+        b.close()
+
+
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(harness, oracles, capsys):
+    """Sized from the device (tests/deal_cases.py, proven on the CPU by tests/test_deal_cases.py): a share of twelve units, so every wave takes three units
+    one after the other -- in the forms that go through LDS, through the same tile --, passes over three one-row destinations in one step, leaves a long
+    destination in the middle of a share and takes a one-block run directly behind a full tile.  The direct form (blocks, natural, int16: eight
+    workgroups a compute unit) and a tiled one (freq, zig-zag, float32: five) get a list of their own.  A dozen distinct components of a few files, listed
+    many times, each entry with a destination of its own; the whole arena of every call against the model."""
+    import jpegsnoop_amd as J
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lists = {"direct": D.coefs_records(cus, "direct"), "tiled": D.coefs_records(cus, "tiled")}
+    for form, recs in lists.items():
+        c = D.census_of("coefs", form, recs, cus)
+        with capsys.disabled():
+            print("\nk_pack_coefs %s, %d compute units: %s" % (form, cus, D.summary(c)))
+        assert D.missing(c, D.KERNELS["coefs"]["waves"], **D.conditions("coefs", form)) == [], D.summary(c)
+    images = sorted({r.pic[:3] for recs in lists.values() for r in recs})
+    files = [harness.synth_jpeg(width=w, height=h, quality=(80, 92)[k % 2], restart_interval=(0, 3)[k % 2], seed=1500 + k, **LAYOUTS[l]) for k, (l, w, h) in enumerate(images)]
+    truths = [Truth(harness, oracles, f) for f in files]
+    T = J.capi.COEF_TILE
+    b = decoded_batch(J, files)
+    try:
+        for form, recs in lists.items():
+            dests = [(images.index(r.pic[:3]), r.pic[3]) for r in recs]
+            for r, (i, comp) in zip(recs, dests):                     # the units the census counted are the units of the call
+                bw, bh = truths[i].geo.grid(comp)
+                assert b.coef_grid(i, comp) == (bw, bh) and r.sizes == ([T] * (-(-bw // T) - 1) + [bw - T * (-(-bw // T) - 1)]) * bh, r.pic
+            pack_and_check(J, torch, b, truths, dests, ("blocks", "int16", False) if form == "direct" else ("freq", "float32", True), what="deal " + form)
     finally:
         b.close()
 

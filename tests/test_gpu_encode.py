@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import coef_model as CM
+import deal_cases as D
 import encode_cases as EC
 import encode_model as M
 import export_model as EM
@@ -53,8 +54,9 @@ def picture(layout, w, h, seed):
     return EC.picture(w, h, seed, grey=layout == "grey")
 
 
-def assert_arena(enc, i, px, layout, tables, what):
-    arena, dccum, geo, _q = M.encode(px, SUB[layout], tables)
+def assert_arena(enc, i, px, layout, tables, what, model=None):
+    """model: M.encode(px, SUB[layout], tables) where the caller has it already."""
+    arena, dccum, geo, _q = model or M.encode(px, SUB[layout], tables)
     a, d = enc.coefs(i)
     assert a.shape == arena.shape, (what, a.shape, arena.shape)
     bad = np.flatnonzero((a != arena).any(1) | (d != dccum))
@@ -152,6 +154,34 @@ def test_the_extreme_pictures(enc, torch, layout):
     pics = [np.ascontiguousarray(p[..., 0]) if layout == "grey" else p for p in EC.extremes().values()]
     run_and_check(enc, torch, pics, layout, layout + " extremes", quality=100)
     run_and_check(enc, torch, pics, layout, layout + " extremes q1", quality=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the deal: a wave walks several units and records
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(enc, torch, capsys):
+    """Every test above stays below EN_WAVES * 4 * compute units units, where a workgroup's share is four units and a wave takes one.  Here the call is
+    sized from the device (tests/deal_cases.py; tests/test_deal_cases.py proves the lists on the CPU): a share of twelve units or more, so every wave
+    takes three and more one after the other through the same LDS, crosses records -- one-MCU pictures four in a row, which one step passes over --,
+    leaves a long picture in the middle of a share and takes a one-MCU run directly behind a run of eight.  About a dozen distinct pictures, many source
+    descriptors on the same tensors; grey and colour in one 4:2:0 call, then a 4:2:2 call with other tables.  Every image against the model."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for form, quality in (("420", 77), ("422", 40)):
+        layout = "4:2:" + form[2]
+        recs = D.encode_records(cus, form)
+        c = D.census_of("encode", form, recs, cus)
+        with capsys.disabled():
+            print("\nk_encode %s, %d compute units: %s" % (layout, cus, D.summary(c)))
+        assert D.missing(c, D.KERNELS["encode"]["waves"], **D.conditions("encode", form)) == [], D.summary(c)
+        tables = M.quality_tables(quality)
+        distinct = sorted({r.pic for r in recs})
+        px = {p: EC.picture(p[1], p[2], 40 + k, grey=p[0] == "grey") for k, p in enumerate(distinct)}
+        model = {p: M.encode(px[p], SUB[layout], tables) for p in distinct}
+        for r in recs:                                                # the units the census counted are the units of the call
+            geo = model[r.pic][2]
+            assert r.units == -(-geo.mcu_x // RUN) * geo.mcu_y and sum(r.sizes) == geo.mcu_x * geo.mcu_y, r.pic
+        dev = {p: torch.from_numpy(px[p]).cuda() for p in distinct}
+        assert enc.run([dev[r.pic] for r in recs], quality=quality, subsampling=layout) == len(recs) == len(enc)
+        for i, r in enumerate(recs):
+            assert_arena(enc, i, px[r.pic], "grey" if r.pic[0] == "grey" else layout, tables, "deal %s image %d %s" % (layout, i, r.pic), model=model[r.pic])
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6: exports, round trip, wrappers

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import coef_model as CM
+import deal_cases as D
 import export_model as EM
 import export_opt_model as OM
 import export_prog_model as PM
@@ -89,7 +90,8 @@ def check_run(t, S, images, what, **opts):
     """The object after run(images, **opts) against the model, entry by entry.  -> the model's results, one per entry."""
     op = M.OPS[opts["op"]] if isinstance(opts["op"], str) else opts["op"]
     edge = {"trim": M.TRIM, "perfect": M.PERFECT}[opts.get("edge", "trim")]
-    want = [M.transform(*S.src[i], op, edge, opts.get("grayscale", False), opts.get("crop")) for i in images]
+    once = {i: M.transform(*S.src[i], op, edge, opts.get("grayscale", False), opts.get("crop")) for i in set(images)}      # (a list may name an image many times)
+    want = [once[i] for i in images]
     ent = t.entries()
     assert [e["result"] for e in ent] == [R.result for R in want], (what, opts, ent)
     k = 0
@@ -173,6 +175,33 @@ def test_a_mixed_call_of_twelve_entries_a_second_run_and_both_stream_arrangement
             check_run(own, S, order, "own stream", op="rot270")
         finally:
             own.close()
+    finally:
+        S.close()
+
+
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(J, torch, capsys):
+    """The calls above stay below XF_WAVES * 8 * compute units units, where a workgroup's share is four units and a wave takes one.  Here the lists are
+    sized from the device (tests/deal_cases.py, proven on the CPU by tests/test_deal_cases.py): a share of twelve units, so every wave takes three runs
+    one after the other -- under a transposing op through the same LDS tile --, passes over three one-run entries in one step, leaves a long entry in
+    the middle of a share and takes a run of fewer than eight blocks directly behind a full one.  flip_v as it comes, and rot90 with a crop and
+    edge="perfect"; entries the call refuses (EMPTY, IMPERFECT) sit among those it writes and get no record.  About twenty distinct files under
+    three table sets, listed many times; every entry against the model."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lists = {form: D.transform_records(cus, form) for form in D.TRANSFORM_FORMS}
+    for form, recs in lists.items():
+        c = D.census_of("transform", form, recs, cus)
+        with capsys.disabled():
+            print("\nk_transform %s, %d compute units: %s" % (D.TRANSFORM_FORMS[form], cus, D.summary(c)))
+        assert D.missing(c, D.KERNELS["transform"]["waves"], **D.conditions("transform", form)) == [], D.summary(c)
+    shapes = sorted({r.pic for recs in lists.values() for r in recs})
+    S = made(J, shapes)
+    try:
+        for form, recs in lists.items():
+            images = [shapes.index(r.pic) for r in recs]
+            want = run_and_check(S, images, "deal " + form, **D.TRANSFORM_FORMS[form])
+            for r, R in zip(recs, want):                              # the units the census counted are the units of the call
+                assert (r.sizes is None) == (R.result != M.OK) and (r.sizes is None or (sum(r.sizes), r.units) == (R.geo.nblocks, -(-R.geo.nblocks // RUN))), r.pic
+            assert {R.result for R in want} == ({M.OK, M.EMPTY, M.IMPERFECT} if form == "turned" else {M.OK, M.EMPTY})
     finally:
         S.close()
 
