@@ -592,6 +592,35 @@ int          jsnoop_batch_plane_size(const JsnoopBatch*, const JsnoopPlaneSpec*,
 uint64_t     jsnoop_batch_plane_bytes(const JsnoopBatch*, const JsnoopPlaneSpec*, int i, int comp);                           /* dense size; 0 = bad argument */
 int          jsnoop_batch_pack_planes(JsnoopBatch*, const JsnoopPlaneSpec*, const int* images, int n, const JsnoopPlaneDst* dst);
 
+/* ---- libjpeg's pixels: a decoded batch rendered with the integer IDCT, fancy upsampling and fixed-point colour, on the device -------------
+ * The seventh sibling.  The DIB holds JPEGsnoop's pixels (fp32 IDCT, replicated chroma, fp32 colour lines); every other decoder a user can
+ * compare with -- Pillow, OpenCV, torchvision, browsers, djpeg -- gives libjpeg's.  jsnoop_batch_pack_ijg renders any subset of a decoded
+ * batch a second time, from the coefficient arena and the cumulative DC, in ONE kernel launch, and stores the result in the forms of
+ * jsnoop_batch_pack: the same JsnoopPackSpec (HWC / CHW, uint8 / float32 with (float)v * scale[c] + bias[c] in two rounded operations,
+ * bgr), the same JsnoopPackDst (dense or pitched rows at any byte alignment for uint8), the sizes of jsnoop_batch_pack_bytes, cropped to the
+ * SOF dimensions, top-down.  Only addressed elements are written.
+ *
+ * What a pixel is (tests/ijg_model.py is the definition).  Per block libjpeg's jidctint ("islow", CONST_BITS 13,
+ * PASS1_BITS 2: columns descaled by 11, then rows by 18, 32-bit wrapping sums), sample = clamp(result + 128, 0, 255) -- libjpeg's pixels
+ * exactly while |result| <= 511, which every file an encoder wrote satisfies.  Chroma of a 2 x 1 / 2 x 2 subsampled image goes through
+ * libjpeg's triangle filter (h2v1 / h2v2 "fancy" upsampling), its neighbours clamped to the component's real extent
+ * ceil(dim_x / 2) x ceil(dim_y / 2 or 1); a chroma plane at most two samples wide is replicated instead, as libjpeg does it.  Colour:
+ * R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), clamped.  A
+ * one-component image gives R = G = B = Y.  The preview mode and the YCC shift of an image descriptor are not applied.
+ *
+ * Renderable: precision 8, and one component, or three taken as Y, Cb, Cr with chroma sampled 1 x 1 and luma 1 x 1, 2 x 1 or 2 x 2
+ * (4:4:4, 4:2:2, 4:2:0).  jsnoop_batch_ijg_renderable says 1, or 0 with the reason in jsnoop_last_error(); host arithmetic only.
+ *
+ * Ordering: jsnoop_batch_pack_coefs', word for word -- enqueued on the batch's stream behind the decode enqueued last (both halves of a
+ * two-stream decode included), not waited for; a call after jsnoop_batch_sync renders the repaired blocks, a call before it what the
+ * parallel path left.  After a DC-only fast-form decode (jsnoop_batch_last_form == 2) the call does what jsnoop_batch_read_coefs does,
+ * decodes the batch once more through the Full-IDCT kernels and waits for it, and jsnoop_batch_last_form says 1 afterwards.
+ *
+ * Refused with -1 + jsnoop_last_error(), nothing launched, nothing written: everything jsnoop_batch_pack refuses, and a listed image that
+ * is not renderable (the text names it and why).  n == 0 is 0; images == NULL means images 0 .. n - 1; any order, subsets and repeats.    */
+int          jsnoop_batch_ijg_renderable(const JsnoopBatch*, int i);
+int          jsnoop_batch_pack_ijg(JsnoopBatch*, const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);
+
 /* ---- export: a decoded batch written back as baseline JPEG files, entropy-coded on the device -------------------------------------------
  * The one product of a decode that is a FILE.  jsnoop_batch_export_jpeg encodes what the batch holds for every listed image -- the
  * coefficient arena and the cumulative DC, so the repaired blocks of a damaged file after jsnoop_batch_sync, the merged scans of a

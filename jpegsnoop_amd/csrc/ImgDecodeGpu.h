@@ -267,6 +267,11 @@ public:
     // (jsnoop_batch_pack: enqueued on the batch's stream, not waited for; jsnoop_pack_spec_defaults fills a spec)
     bool     BatchPack(const JsnoopPackSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    // the listed files rendered as libjpeg's pixels (integer IDCT, fancy upsampling, fixed-point colour) from the coefficient arena, in BatchPack's store forms
+    // (jsnoop_batch_pack_ijg: one launch for the whole list, same ordering; BatchIjgRenderable: whether a file's layout is rendered, host arithmetic)
+    bool     BatchPackIjg(const JsnoopPackSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack_ijg(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
+    bool     BatchIjgRenderable(int nFileInd) const { return jsnoop_batch_ijg_renderable(m_b, nFileInd) == 1; }
     // (jsnoop_batch_pack_resized: a rectangle of every listed file at its destination's size, filter = JSNOOP_RESIZE_*; same ordering)
     bool     BatchPackResized(const JsnoopPackSpec& spec, int filter, const std::vector<int>& files, const std::vector<JsnoopResizeDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_resized(m_b, &spec, filter, files.data(), (int)files.size(), dst.data()) == 0; }

@@ -175,3 +175,9 @@ int  js_launch_carve_count(hipStream_t st, const uint8_t* base, uint32_t head, u
 // ... second phase: k_carve_emit writes the two ascending position lists, k_carve_walk one 64-byte record per candidate.
 int  js_launch_carve_walk(hipStream_t st, const uint8_t* base, uint32_t head, uint64_t n, uint32_t tiles, const uint32_t* counts, uint32_t nterm, uint32_t ncand,
                           uint32_t max_markers, uint32_t* term, uint32_t* cand, uint32_t* recs);
+// k_render_ijg (jsnoop_render.hip): the coefficient arena of a decoded batch rendered as libjpeg's pixels -> caller-owned device memory, jsnoop_batch_pack's store
+// forms, ONE launch for the whole list.  recs / unit_base: JsRenRec and its prefix table (jsnoop_render_check.h), both in device memory.  0, -1 on a launch error
+// or an unknown layout / dtype.
+struct JsRenRec;
+int  js_launch_render_ijg(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsRenRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                          int layout /*JSNOOP_PACK_HWC / _CHW*/, int dtype /*JSNOOP_PACK_U8 / _F32*/, const JsPackArgs& a);

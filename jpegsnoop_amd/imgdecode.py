@@ -250,7 +250,7 @@ class JpegBatch:
         return int(self._lib.jsnoop_batch_pack_bytes(self._h, C.byref(spec), i))
 
     def to_torch(self, images=None, layout="CHW", dtype=None, bgr=False, scale=None, bias=None, stack=False, pad_to=None, out=None,
-                 size=None, filter="bilinear", roi=None):
+                 size=None, filter="bilinear", roi=None, pixels="jpegsnoop"):
         """The decoded images as torch tensors on the batch's device: cropped to the SOF dimensions, top-down, three channels (R,G,B, or
         B,G,R with bgr), filled by ONE jsnoop_batch_pack -- no pixel crosses PCIe.
 
@@ -267,6 +267,11 @@ class JpegBatch:
         reducing).  roi: None (whole images), one (x, y, w, h) for all, or a list with one per image, in the coordinates of the cropped
         top-down image.  With H x W equal to the rectangle's size every filter returns its pixels unchanged.  size= excludes stack and pad_to;
         filter (other than the default) or roi without size= is a ValueError.
+
+        pixels: "jpegsnoop" (default) -- the DIB's bytes: JPEGsnoop's fp32 IDCT, replicated chroma, fp32 colour lines; "libjpeg" -- the batch rendered a
+        second time from its coefficients by ONE jsnoop_batch_pack_ijg: the integer "islow" IDCT, fancy chroma upsampling and 16-bit fixed-point
+        colour, the pixels Pillow, OpenCV, torchvision and djpeg give for the same file.  Every image listed must be renderable
+        (ijg_renderable); size= and roi= are refused with "libjpeg" for now.
 
         Calls sync() first (damaged files arrive repaired), synchronises torch's current stream before the pack unless the batch runs on it, and
         waits for the batch's stream -- sync() again, no other stream of the device is waited for -- before it returns: the tensors are ready."""
@@ -287,6 +292,10 @@ class JpegBatch:
             raise ValueError("to_torch: stack, pad_to and out exclude each other")
         if size is None and (roi is not None or filter != "bilinear"):
             raise ValueError("to_torch: filter and roi belong to size=(H, W)")
+        if pixels not in ("jpegsnoop", "libjpeg"):
+            raise ValueError("to_torch: pixels must be \"jpegsnoop\" or \"libjpeg\"")
+        if pixels == "libjpeg" and (size is not None or roi is not None):
+            raise ValueError("to_torch: size= and roi= are not available with pixels=\"libjpeg\"")
         spec = _pack_spec(self._lib, layout, is_f32, bgr, scale, bias)
         chw = layout == "CHW"
         self.sync()
@@ -356,9 +365,17 @@ class JpegBatch:
         if self._stream != cur.cuda_stream:
             cur.synchronize()
         ind = (C.c_int * len(idx))(*idx)
-        self._chk(self._lib.jsnoop_batch_pack(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack")
+        if pixels == "libjpeg":
+            self._chk(self._lib.jsnoop_batch_pack_ijg(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack_ijg")
+        else:
+            self._chk(self._lib.jsnoop_batch_pack(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack")
         self.sync()                              # waits for the batch's stream alone
         return result
+
+    def ijg_renderable(self, i) -> bool:
+        """Whether to_torch(pixels="libjpeg") renders image i (jsnoop_batch_ijg_renderable: precision 8; one component, or Y Cb Cr as 4:4:4, 4:2:2
+        or 4:2:0).  Host arithmetic; False leaves the reason in last_error()."""
+        return int(self._lib.jsnoop_batch_ijg_renderable(self._h, int(i))) == 1
 
     def _to_torch_resized(self, torch, idx, spec, chw, dtype, dev, stack, pad_to, out, size, filter, roi):
         """to_torch(size=...): one [N, ...] tensor filled by one jsnoop_batch_pack_resized.  The batch has been synchronised."""
