@@ -621,6 +621,28 @@ int          jsnoop_batch_pack_planes(JsnoopBatch*, const JsnoopPlaneSpec*, cons
 int          jsnoop_batch_ijg_renderable(const JsnoopBatch*, int i);
 int          jsnoop_batch_pack_ijg(JsnoopBatch*, const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);
 
+/* ---- libjpeg's pixels at 1/2, 1/4, 1/8 size: the scaled IDCTs, on the device ----------------------------------------------------------------
+ * What Image.draft / Image.thumbnail, cv2.IMREAD_REDUCED_COLOR_2/4/8 and djpeg -scale 1/N give: the blocks go through libjpeg's smaller
+ * inverse transforms (jidctred.c: 4 x 4, 2 x 2, 1 x 1), full-size pixels are never made.  jsnoop_batch_pack_ijg_scaled is
+ * jsnoop_batch_pack_ijg with a denominator: denom 1 IS that call (the same launch, the same bytes); denom 2, 4, 8 render image i as
+ * ceil(dim_x / denom) x ceil(dim_y / denom) pixels, top-down, in ONE launch (k_render_ijg_scaled), through the same JsnoopPackSpec /
+ * JsnoopPackDst with sizes and pitches taken against the reduced picture.  Any other denom is refused.
+ *
+ * What a pixel is (tests/ijg_scaled_model.py is the definition, equal to Pillow's draft()ed decode byte for byte).
+ * m = 8 / denom.  A component is transformed at n = m, doubled while n < 8 and both (hmax m) % (h n 2) and (vmax m) % (v n 2) are 0
+ * (jdmaster.c): grey, 4:4:4 and all of 4:2:2 at m; 4:2:0 luma at m and chroma at 2 m -- the MCU's output size, so 4:2:0 chroma is not
+ * upsampled at all.  Pass 1 along the columns, pass 2 along the n rows, CONST_BITS 13, PASS1_BITS 2, 32-bit wrapping sums,
+ * sample = clamp(result + 128, 0, 255); the 1 x 1 is DESCALE(dc, 3).  4:2:2 chroma goes through the h2v1 triangle filter on the reduced
+ * plane at denom 2 and 4 (neighbours clamped to the plane's real width, a plane at most two samples wide replicated) and is replicated at
+ * denom 8, where libjpeg has no filter.  The colour lines are jsnoop_batch_pack_ijg's.
+ *
+ * Ordering, the re-decode behind a DC-only fast form, the renderable layouts and every refusal (-1 + jsnoop_last_error(), nothing launched,
+ * nothing written) are jsnoop_batch_pack_ijg's.  jsnoop_batch_ijg_scaled_size gives the reduced size of a renderable image (host arithmetic),
+ * jsnoop_batch_pack_ijg_scaled_bytes the dense size of its destination.                                                                     */
+int          jsnoop_batch_ijg_scaled_size(const JsnoopBatch*, int i, unsigned denom, unsigned* w, unsigned* h);                /* host arithmetic; 0 / -1 */
+uint64_t     jsnoop_batch_pack_ijg_scaled_bytes(const JsnoopBatch*, const JsnoopPackSpec*, unsigned denom, int i);             /* dense size; 0 = bad argument */
+int          jsnoop_batch_pack_ijg_scaled(JsnoopBatch*, const JsnoopPackSpec* spec, unsigned denom, const int* images, int n, const JsnoopPackDst* dst);
+
 /* ---- export: a decoded batch written back as baseline JPEG files, entropy-coded on the device -------------------------------------------
  * The one product of a decode that is a FILE.  jsnoop_batch_export_jpeg encodes what the batch holds for every listed image -- the
  * coefficient arena and the cumulative DC, so the repaired blocks of a damaged file after jsnoop_batch_sync, the merged scans of a

@@ -467,6 +467,9 @@ SIGNATURES = {
     "jsnoop_batch_pack_planes": (_i, [_p, C.POINTER(PlaneSpec), _PI, _i, C.POINTER(PlaneDst)]),
     "jsnoop_batch_ijg_renderable": (_i, [_p, _i]),
     "jsnoop_batch_pack_ijg": (_i, [_p, C.POINTER(PackSpec), _PI, _i, C.POINTER(PackDst)]),
+    "jsnoop_batch_ijg_scaled_size": (_i, [_p, _i, C.c_uint, _PU, _PU]),
+    "jsnoop_batch_pack_ijg_scaled_bytes": (C.c_uint64, [_p, C.POINTER(PackSpec), C.c_uint, _i]),
+    "jsnoop_batch_pack_ijg_scaled": (_i, [_p, C.POINTER(PackSpec), C.c_uint, _PI, _i, C.POINTER(PackDst)]),
     "jsnoop_export_spec_defaults": (None, [C.POINTER(ExportSpec)]),
     "jsnoop_batch_export_jpeg": (_i, [_p, C.POINTER(ExportSpec), _PI, _i]),
     "jsnoop_batch_export_count": (_i, [_p]),

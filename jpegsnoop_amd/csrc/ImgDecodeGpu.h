@@ -272,6 +272,11 @@ public:
     bool     BatchPackIjg(const JsnoopPackSpec& spec, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_ijg(m_b, &spec, files.data(), (int)files.size(), dst.data()) == 0; }
     bool     BatchIjgRenderable(int nFileInd) const { return jsnoop_batch_ijg_renderable(m_b, nFileInd) == 1; }
+    // ... at 1 / nDenom of the size (nDenom 1, 2, 4, 8: libjpeg's scaled IDCTs, what djpeg -scale 1/N and Image.draft give; 1 is BatchPackIjg), into destinations of
+    // BatchIjgScaledSize's dimensions (jsnoop_batch_pack_ijg_scaled: one launch for the whole list, same ordering)
+    bool     BatchPackIjgScaled(const JsnoopPackSpec& spec, unsigned nDenom, const std::vector<int>& files, const std::vector<JsnoopPackDst>& dst)
+    { return files.size() == dst.size() && jsnoop_batch_pack_ijg_scaled(m_b, &spec, nDenom, files.data(), (int)files.size(), dst.data()) == 0; }
+    bool     BatchIjgScaledSize(int nFileInd, unsigned nDenom, unsigned& nW, unsigned& nH) const { return jsnoop_batch_ijg_scaled_size(m_b, nFileInd, nDenom, &nW, &nH) == 0; }
     // (jsnoop_batch_pack_resized: a rectangle of every listed file at its destination's size, filter = JSNOOP_RESIZE_*; same ordering)
     bool     BatchPackResized(const JsnoopPackSpec& spec, int filter, const std::vector<int>& files, const std::vector<JsnoopResizeDst>& dst)
     { return files.size() == dst.size() && jsnoop_batch_pack_resized(m_b, &spec, filter, files.data(), (int)files.size(), dst.data()) == 0; }

@@ -129,6 +129,7 @@ struct JsnoopBatch {
     int  pack_resized(const JsnoopPackSpec* spec, int filter, const int* images, int n, const JsnoopResizeDst* dst);   // jsnoop_pack.cpp; the same block and event
     int  pack_coefs(const JsnoopCoefSpec* spec, const int* images, int n, const JsnoopCoefDst* dst);   // jsnoop_coef.cpp; the same block and event
     int  pack_ijg(const JsnoopPackSpec* spec, const int* images, int n, const JsnoopPackDst* dst);   // jsnoop_render.cpp; the same block and event
+    int  pack_ijg_scaled(const JsnoopPackSpec* spec, unsigned denom, const int* images, int n, const JsnoopPackDst* dst);   // jsnoop_render_scaled.cpp; the same block and event
     int  pack_stats(int histo_en, const int* images, int n, void* dst, uint64_t row_pitch_words, uint32_t* totals);   // jsnoop_stats.cpp; the same block and event
     int  read_stats(int histo_en, const int* images, int n, uint32_t* host_dst);                   // ... into batch-owned device scratch, one D2H, one wait
     uint8_t* d_stats = nullptr; size_t d_stats_cap = 0;           // scratch of pack_stats (event totals, events per picture row), grown on demand

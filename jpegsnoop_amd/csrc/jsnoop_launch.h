@@ -181,3 +181,9 @@ int  js_launch_carve_walk(hipStream_t st, const uint8_t* base, uint32_t head, ui
 struct JsRenRec;
 int  js_launch_render_ijg(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsRenRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
                           int layout /*JSNOOP_PACK_HWC / _CHW*/, int dtype /*JSNOOP_PACK_U8 / _F32*/, const JsPackArgs& a);
+// k_render_ijg_scaled (jsnoop_render_scaled.hip): ... as libjpeg's reduced-size pixels (1/2, 1/4, 1/8; the scale is in the records), the same store forms, ONE launch
+// for the whole list.  recs / unit_base: JsRsRec and its prefix table (jsnoop_render_scaled_check.h), both in device memory.  0, -1 on a launch error or an unknown
+// layout / dtype.
+struct JsRsRec;
+int  js_launch_render_ijg_scaled(hipStream_t st, const int16_t* coef, const int16_t* dccum, const JsRsRec* recs, const uint32_t* unit_base, uint32_t nrec, uint32_t total_units,
+                                 int layout /*JSNOOP_PACK_HWC / _CHW*/, int dtype /*JSNOOP_PACK_U8 / _F32*/, const JsPackArgs& a);

@@ -250,7 +250,7 @@ class JpegBatch:
         return int(self._lib.jsnoop_batch_pack_bytes(self._h, C.byref(spec), i))
 
     def to_torch(self, images=None, layout="CHW", dtype=None, bgr=False, scale=None, bias=None, stack=False, pad_to=None, out=None,
-                 size=None, filter="bilinear", roi=None, pixels="jpegsnoop"):
+                 size=None, filter="bilinear", roi=None, pixels="jpegsnoop", reduce=1):
         """The decoded images as torch tensors on the batch's device: cropped to the SOF dimensions, top-down, three channels (R,G,B, or
         B,G,R with bgr), filled by ONE jsnoop_batch_pack -- no pixel crosses PCIe.
 
@@ -272,6 +272,11 @@ class JpegBatch:
         second time from its coefficients by ONE jsnoop_batch_pack_ijg: the integer "islow" IDCT, fancy chroma upsampling and 16-bit fixed-point
         colour, the pixels Pillow, OpenCV, torchvision and djpeg give for the same file.  Every image listed must be renderable
         (ijg_renderable); size= and roi= are refused with "libjpeg" for now.
+
+        reduce: 1 (default), 2, 4 or 8 -- with pixels="libjpeg", libjpeg's reduced-size decode (the scaled IDCTs: what Image.draft, cv2.IMREAD_REDUCED_COLOR_*
+        and djpeg -scale 1/N give): image i arrives as ceil(dim_y / reduce) x ceil(dim_x / reduce) (ijg_scaled_size), and every size above -- stack, pad_to,
+        out -- is taken against that.  A sequence gives one value per listed image (reduce_for turns a target size into one); the list is then served by at
+        most four jsnoop_batch_pack_ijg_scaled, one per value.  reduce other than 1 without pixels="libjpeg" is a ValueError.
 
         Calls sync() first (damaged files arrive repaired), synchronises torch's current stream before the pack unless the batch runs on it, and
         waits for the batch's stream -- sync() again, no other stream of the device is waited for -- before it returns: the tensors are ready."""
@@ -296,6 +301,16 @@ class JpegBatch:
             raise ValueError("to_torch: pixels must be \"jpegsnoop\" or \"libjpeg\"")
         if pixels == "libjpeg" and (size is not None or roi is not None):
             raise ValueError("to_torch: size= and roi= are not available with pixels=\"libjpeg\"")
+        if isinstance(reduce, (list, tuple)):
+            red = [int(x) for x in reduce]
+            if len(red) != len(idx):
+                raise ValueError(f"to_torch: reduce holds {len(red)} values for {len(idx)} images")
+        else:
+            red = [int(reduce)] * len(idx)
+        if any(x not in (1, 2, 4, 8) for x in red) or (not isinstance(reduce, (list, tuple)) and int(reduce) not in (1, 2, 4, 8)):
+            raise ValueError("to_torch: reduce must be 1, 2, 4 or 8")
+        if pixels != "libjpeg" and (isinstance(reduce, (list, tuple)) or int(reduce) != 1):
+            raise ValueError("to_torch: reduce belongs to pixels=\"libjpeg\"")
         spec = _pack_spec(self._lib, layout, is_f32, bgr, scale, bias)
         chw = layout == "CHW"
         self.sync()
@@ -303,7 +318,10 @@ class JpegBatch:
         if size is not None:
             return self._to_torch_resized(torch, idx, spec, chw, dtype, dev, stack, pad_to, out, size, filter, roi)
         dims = []
-        for i in idx:
+        for k, i in enumerate(idx):
+            if red[k] != 1:
+                dims.append(self.ijg_scaled_size(i, red[k]))
+                continue
             inf = self.info(i)
             dims.append((inf["dim_y"], inf["dim_x"]))
         shape = (lambda h, w: (3, h, w)) if chw else (lambda h, w: (h, w, 3))
@@ -365,7 +383,15 @@ class JpegBatch:
         if self._stream != cur.cuda_stream:
             cur.synchronize()
         ind = (C.c_int * len(idx))(*idx)
-        if pixels == "libjpeg":
+        if pixels == "libjpeg" and any(x != 1 for x in red):
+            for denom in sorted(set(red)):                        # one call per value: at most four
+                ks = [k for k in range(len(idx)) if red[k] == denom]
+                sub = (capi.PackDst * len(ks))()
+                for j, k in enumerate(ks):
+                    sub[j].ptr, sub[j].row_pitch, sub[j].plane_pitch = dst[k].ptr, dst[k].row_pitch, dst[k].plane_pitch
+                self._chk(self._lib.jsnoop_batch_pack_ijg_scaled(self._h, C.byref(spec), denom, (C.c_int * len(ks))(*[idx[k] for k in ks]), len(ks), sub),
+                          "batch_pack_ijg_scaled")
+        elif pixels == "libjpeg":
             self._chk(self._lib.jsnoop_batch_pack_ijg(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack_ijg")
         else:
             self._chk(self._lib.jsnoop_batch_pack(self._h, C.byref(spec), ind, len(idx), dst), "batch_pack")
@@ -376,6 +402,23 @@ class JpegBatch:
         """Whether to_torch(pixels="libjpeg") renders image i (jsnoop_batch_ijg_renderable: precision 8; one component, or Y Cb Cr as 4:4:4, 4:2:2
         or 4:2:0).  Host arithmetic; False leaves the reason in last_error()."""
         return int(self._lib.jsnoop_batch_ijg_renderable(self._h, int(i))) == 1
+
+    def ijg_scaled_size(self, i, reduce):
+        """(h, w) of image i as to_torch(pixels="libjpeg", reduce=reduce) gives it: ceil(dim_y / reduce), ceil(dim_x / reduce)
+        (jsnoop_batch_ijg_scaled_size; host arithmetic).  RuntimeError for an image that is not renderable or a reduce other than 1, 2, 4, 8."""
+        w, h = C.c_uint(0), C.c_uint(0)
+        self._chk(self._lib.jsnoop_batch_ijg_scaled_size(self._h, int(i), int(reduce), C.byref(w), C.byref(h)), "batch_ijg_scaled_size")
+        return int(h.value), int(w.value)
+
+    def reduce_for(self, i, size) -> int:
+        """The denominator Pillow's Image.draft chooses for image i and a target size=(H, W): the largest of 8, 4, 2, 1 not above
+        min(dim_x // W, dim_y // H) -- the smallest reduced picture that is still at least as large as the target."""
+        H, W = int(size[0]), int(size[1])
+        if H < 1 or W < 1:
+            raise ValueError("reduce_for: size must be (H, W), each at least 1")
+        inf = self.info(int(i))
+        q = min(inf["dim_x"] // W, inf["dim_y"] // H)
+        return next(s for s in (8, 4, 2, 1) if q >= s or s == 1)
 
     def _to_torch_resized(self, torch, idx, spec, chw, dtype, dev, stack, pad_to, out, size, filter, roi):
         """to_torch(size=...): one [N, ...] tensor filled by one jsnoop_batch_pack_resized.  The batch has been synchronised."""
@@ -1460,7 +1503,7 @@ class JobFileResult:
 
     def to_torch(self, **kw):
         """JpegBatch.to_torch for this file alone: one tensor ([3, dim_y, dim_x] / [dim_y, dim_x, 3]; with stack / pad_to / size / a tensor out,
-        the [1, ...] tensor).  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
+        the [1, ...] tensor); pixels="libjpeg" and reduce= pass through like every keyword.  Valid inside the callback, or until JpegJob.clear() / close() with keep_resident."""
         if self.batch is None:
             raise RuntimeError("to_torch: this result holds no resident image (status %s)" % self.status)
         r = self.batch.to_torch(images=[self.image], **kw)
