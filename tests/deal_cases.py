@@ -1,8 +1,9 @@
-"""The unit deal that eight kernels copy, restated and simulated -- TEST INFRASTRUCTURE behind tests/test_deal_cases.py (CPU) and one GPU test in each of
-test_gpu_encode.py, test_gpu_transform.py, test_gpu_coefs.py, test_gpu_batch_stats.py and test_gpu_coef_hist.py.
+"""The unit deal that ten kernels copy, restated and simulated -- TEST INFRASTRUCTURE behind tests/test_deal_cases.py (CPU) and one GPU test in each of
+test_gpu_encode.py, test_gpu_transform.py, test_gpu_coefs.py, test_gpu_batch_stats.py, test_gpu_coef_hist.py, test_gpu_pack_ijg.py and
+test_gpu_pack_ijg_scaled.py: seven kernels have a test sized here; k_pack_rgb, k_pack_planes and k_pack_resize rely on their 1080p tests.
 
 A launcher lays the units of all records of a call end to end over a prefix table and gives a workgroup a contiguous share of
-S = ceil(T / min(F * cus, ceil(T / W))) units.  In k_encode, k_transform, k_pack_coefs and k_stats_batch wave w of the workgroup takes units
+S = ceil(T / min(F * cus, ceil(T / W))) units.  In k_encode, k_transform, k_pack_coefs, k_stats_batch, k_render_ijg and k_render_ijg_scaled wave w takes units
 u0 + w, u0 + w + W, ...: it finds the record of its first unit by a binary search and moves on with `while (u >= unit_base[k + 1]) k++`.  k_coef_hist
 walks its share destination by destination, and its W waves interleave inside one destination (`by_record`).  While T <= W * F * cus a share is W units,
 a wave takes one unit and none of this happens; `census` says what does happen for a given record list, and the builders below make record lists for
@@ -15,6 +16,12 @@ The constants, and where the sources state them (KERNELS / SOURCE; the CPU test 
   coefs        jsnoop_coef.hip:35, :93                 jsnoop_coef.hip:187 (direct / through a tile)   jsnoop_types.h:159 JS_COEF_TILE blocks of a block row
   stats        jsnoop_stats.hip:35, :126               jsnoop_stats.hip:262 (histograms / none)        jsnoop_types.h:165 JS_STATS_UNIT pixels of a picture row
   coef_hist    jsnoop_types.h:174, jsnoop_coef_hist.hip:83   jsnoop_types.h:175                        jsnoop_types.h:173 JS_COEF_HIST_UNIT blocks, arena order
+  render       jsnoop_render.hip:31, :129              jsnoop_render.hip:219                           jsnoop_render_check.h:71 JS_REN_RUN MCUs of an MCU row
+  render_scaled  jsnoop_render_scaled.hip:26, :138     jsnoop_render_scaled.hip:176                    jsnoop_render_scaled_check.h:135 js_rs_run: 64 reduced pixels of an MCU row
+
+The two renders keep the most in LDS from unit to unit (luma rectangle, chroma planes with halo columns and rows, transpose tile, workspace), and what a
+unit leaves there depends on its picture's layout.  Their lists are therefore also asked for ADJACENT: which kind of unit a wave takes directly behind
+which (`adjacency_missing` walks the simulated wave order; the builders search until it is empty and assert it).
 
 A record list is built from about a dozen distinct pictures: a few long ones that carry the volume and short ones of 1, 2, 3 and 5 units (k_stats_batch:
 block rows, a record is never less than eight picture rows) between them, among them a stretch of one-unit records several shares long.  A builder
@@ -25,6 +32,7 @@ from __future__ import annotations
 import bisect
 from types import SimpleNamespace
 
+import ijg_cases as IC
 import transform_model as TM
 
 KERNELS = {
@@ -33,6 +41,8 @@ KERNELS = {
     "coefs": dict(waves=4, per_cu={"direct": 8, "tiled": 5}, unit=64, by_record=False),
     "stats": dict(waves=4, per_cu={"hist": 4, "plain": 8}, unit=512, by_record=False),
     "coef_hist": dict(waves=8, per_cu={"any": 2}, unit=64, by_record=True),
+    "render": dict(waves=4, per_cu={"any": 6}, unit=8, by_record=False),
+    "render_scaled": dict(waves=4, per_cu={"any": 6}, unit=64, by_record=False),
 }
 # (file, line, text of that line) per kernel, written with the numbers of KERNELS
 _K = KERNELS
@@ -58,6 +68,14 @@ SOURCE = {
                   ("jsnoop_types.h", 175, "#define JS_COEF_HIST_WG_PER_CU %du" % _K["coef_hist"]["per_cu"]["any"]),
                   ("jsnoop_coef_hist.hip", 154, "(uint64_t)cus * std::min(JS_COEF_HIST_WG_PER_CU, CH_LDS_PER_CU / lds), (total_units + CH_WAVES - 1u) / CH_WAVES)"),
                   ("jsnoop_types.h", 173, "#define JS_COEF_HIST_UNIT %du" % _K["coef_hist"]["unit"])],
+    "render": [("jsnoop_render.hip", 30, "#define RN_THREADS %d" % (64 * _K["render"]["waves"])), ("jsnoop_render.hip", 31, "#define RN_WAVES   (RN_THREADS / 64)"),
+               ("jsnoop_render.hip", 129, "for (; u < u1; u += RN_WAVES)"), ("jsnoop_render.hip", 131, "while (u >= unit_base[k + 1]) k++;"),
+               ("jsnoop_render.hip", 219, "std::min<uint64_t>((uint64_t)cus * %du, ((uint64_t)total_units + RN_WAVES - 1u) / RN_WAVES)" % _K["render"]["per_cu"]["any"]),
+               ("jsnoop_render_check.h", 71, "#define JS_REN_RUN      %du" % _K["render"]["unit"])],
+    "render_scaled": [("jsnoop_render_scaled.hip", 25, "#define RS_THREADS %d" % (64 * _K["render_scaled"]["waves"])), ("jsnoop_render_scaled.hip", 26, "#define RS_WAVES   (RS_THREADS / 64)"),
+                      ("jsnoop_render_scaled.hip", 138, "for (; un < u1; un += RS_WAVES)"), ("jsnoop_render_scaled.hip", 140, "while (un >= unit_base[k + 1]) k++;"),
+                      ("jsnoop_render_scaled.hip", 176, "std::min<uint64_t>((uint64_t)cus * %du, ((uint64_t)total_units + RS_WAVES - 1u) / RS_WAVES)" % _K["render_scaled"]["per_cu"]["any"]),
+                      ("jsnoop_render_scaled_check.h", 135, "inline uint32_t js_rs_run(uint32_t H, uint32_t m) { return %du / (H * m); }" % _K["render_scaled"]["unit"])],
 }
 CUS = (64, 104, 228, 256, 304)                                      # the devices the CPU test proves the builders for
 
@@ -167,9 +185,10 @@ class Rec:
         self.units = len(sizes) if isinstance(sizes, list) else 0
 
 
-def _arrange(shorts, longs, refused, n_long, tail, waves):
+def _arrange(shorts, longs, refused, n_long, tail, waves, prelude=()):
     """pictures -> the order of the call.  shorts: {units: [pic]} with 1 (STEP for stats), 2, 3 and 5 (times STEP); the first long record, a stretch of
-    12 W smallest records, a long one, every short one three times over, then long ones with five short ones behind every third, `tail` smallest ones."""
+    12 W smallest records, a long one, every short one three times over, the `prelude` as it stands, then long ones with five short ones behind every
+    third, `tail` smallest ones."""
     small = sorted(shorts)
     ones = shorts[small[0]]; every = [p for n in small for p in shorts[n]]
     seq = [longs[0]] + [ones[i % len(ones)] for i in range(12 * waves)] + [longs[1 % len(longs)]]
@@ -177,6 +196,7 @@ def _arrange(shorts, longs, refused, n_long, tail, waves):
         seq.append(every[i % len(every)])
         if refused and i % 4 == 1:
             seq.append(refused[(i // 4) % len(refused)])
+    seq += list(prelude)
     for i in range(n_long):
         seq.append(longs[(i + 2) % len(longs)])
         if i % 3 == 2:
@@ -199,21 +219,25 @@ def _pick(cands, sizes_of, wanted, full, per=2):
     return shorts, refused
 
 
-def _build(kernel, form, cus, cands, longs, sizes_of, wanted=(1, 2, 3, 5)):
+def _build(kernel, form, cus, cands, longs, sizes_of, wanted=(1, 2, 3, 5), per=2, prelude=(), also=None):
+    """also(recs, cus) -> further conditions the list does not meet, by name: searched for like those of `missing`."""
     K = KERNELS[kernel]; W = K["waves"]; F = K["per_cu"][per_cu_form(kernel, form)]; need = conditions(kernel, form)
-    shorts, refused = _pick(cands, sizes_of, wanted, K["unit"])
-    size = {p: sizes_of(p) for p in set(cands) | set(longs)}
+    shorts, refused = _pick(cands, sizes_of, wanted, K["unit"], per)
+    size = {p: sizes_of(p) for p in set(cands) | set(longs) | set(prelude)}
     assert all(isinstance(size[p], list) and len(size[p]) >= 4 * 3 * W for p in longs), "a long record is more than three shares"
-    fixed = sum(len(size[p]) for p in _arrange(shorts, longs, [], 0, 0, W))                   # (without the refused entries)
+    fixed = sum(len(size[p]) for p in _arrange(shorts, longs, [], 0, 0, W, prelude))          # (without the refused entries)
     per_long = sum(len(size[p]) for p in longs) / len(longs)
     first = max(0, int(((3 * W - 1) * F * cus - fixed) / per_long) - 1)
     for n_long in range(first, first + 12):
         for tail in range(3 * W):
-            recs = [Rec(p, size[p]) for p in _arrange(shorts, longs, refused, n_long, tail, W)]
+            recs = [Rec(p, size[p]) for p in _arrange(shorts, longs, refused, n_long, tail, W, prelude)]
             c = census_of(kernel, form, recs, cus)
-            if not missing(c, W, **need):
+            lacks = missing(c, W, **need)
+            if not lacks and also is not None:
+                lacks = also(recs, cus)
+            if not lacks:
                 return recs
-    raise AssertionError("%s %s at %d compute units: no list meets the conditions, last: %s" % (kernel, form, cus, missing(c, W, **need)))
+    raise AssertionError("%s %s at %d compute units: no list meets the conditions, last: %s" % (kernel, form, cus, lacks))
 
 
 def census_of(kernel, form, recs, cus):
@@ -228,8 +252,8 @@ def conditions(kernel, form):
     k_stats_batch: a record is at least eight picture rows, two steps of four units, so no step passes over a record -- a share must hold three records; a
     unit's size changes nothing.  k_coef_hist: a share is walked record by record, `k++` once a record -- a share must hold four records, a record of 3 S
     units or more must have units in three shares.  The direct form of k_pack_coefs and the non-transposing k_transform keep nothing in LDS from unit to
-    unit: no narrow unit is asked for."""
-    return {"encode": dict(narrow=True), "transform": dict(narrow=form == "turned"), "coefs": dict(narrow=form == "tiled"), "stats": dict(skip=0, held=3),
+    unit: no narrow unit is asked for.  The two renders reuse all of a wave's LDS: a narrow unit, and `adjacency_missing` besides."""
+    return {"render": dict(narrow=True), "render_scaled": dict(narrow=True), "encode": dict(narrow=True), "transform": dict(narrow=form == "turned"), "coefs": dict(narrow=form == "tiled"), "stats": dict(skip=0, held=3),
             "coef_hist": dict(skip=0, held=4, span=3)}[kernel]
 
 
@@ -331,7 +355,135 @@ def coef_hist_records(cus, form="any"):
     return _build("coef_hist", "any", cus, COEF_HIST_SHORT, COEF_HIST_LONG, coef_hist_sizes)
 
 
-BUILDERS = {("encode", "420"): lambda cus: encode_records(cus, "420"), ("encode", "422"): lambda cus: encode_records(cus, "422"),
+# ---- k_render_ijg, k_render_ijg_scaled: pic = (mode of ijg_cases.MODES, width, height); denom 1 is the full-size render, 2 | 4 | 8 the scaled one
+def render_grid(pic, denom=1):
+    """(H, V, MCUs across, MCU rows, MCUs of a full run, runs of an MCU row): js_ren_units / js_rs_units are rows * runs."""
+    mode, w, h = pic; H, V = IC.HV[mode][0]
+    mx, my = -(-w // (8 * H)), -(-h // (8 * V))
+    run = KERNELS["render"]["unit"] if denom == 1 else KERNELS["render_scaled"]["unit"] // (H * (8 // denom))
+    return H, V, mx, my, run, -(-mx // run)
+
+
+def render_sizes(pic):
+    """The MCUs of every unit of the picture."""
+    _H, _V, mx, my, run, runs = render_grid(pic)
+    return ([run] * (runs - 1) + [mx - run * (runs - 1)]) * my
+
+
+def render_scaled_sizes(pic, denom):
+    """The reduced pixels (MCU-padded) every unit of the picture is wide: nm * H * m."""
+    H, _V, mx, my, run, runs = render_grid(pic, denom); m = 8 // denom
+    return ([run * H * m] * (runs - 1) + [(mx - run * (runs - 1)) * H * m]) * my
+
+
+def render_chroma(pic, denom=1):
+    """(the width in samples the chroma filter clamps to, whether the picture's units are filtered horizontally).  Full size: dw = ceil(X / H), H = 2 is
+    filtered from dw = 3 on and replicated below (js_ren_chroma4).  Scaled: 4:2:2 alone at denom 2 and 4, dwc = ceil(X nc / 16) with nc = m (js_rs_chroma4)."""
+    mode, w, _h = pic; H, V = IC.HV[mode][0]
+    if denom == 1:
+        dw = -(-w // H)
+        return dw, mode != "grey" and H == 2 and dw > 2
+    m = 8 // denom; dw = -(-w * m // 16)
+    return dw, mode == "422" and m > 1 and dw > 2
+
+
+def render_filters(denom):
+    return denom in (1, 2, 4)                                       # (at denom 8 nothing is filtered: 4:2:2 chroma is replicated)
+
+
+ADJACENT = ("a grey unit behind a colour unit", "a 4:4:4 unit behind a 4:2:0 unit", "a 4:2:0 unit behind a 4:2:2 unit", "a first MCU row behind an interior unit of 4:2:0",
+            "a last MCU row behind an interior unit of 4:2:0", "a chroma width of 2 or less behind a filtered unit", "a chroma width of 3 behind a filtered unit")
+
+
+def _kinds(pic, denom):
+    """Per unit of the picture what the adjacency conditions ask of it: (mode, interior row of 4:2:0, first row of 4:2:0, last row of 4:2:0, filtered, chroma width)."""
+    mode = pic[0]; H, _V, _mx, my, _run, runs = render_grid(pic, denom); dw, filtered = render_chroma(pic, denom)
+    narrow = dw if (H == 2 and (denom == 1 or mode == "422")) else 0
+    tall = mode == "420" and my >= 2
+    return [(mode, mode == "420" and my >= 3 and 0 < y < my - 1, tall and y == 0, tall and y == my - 1, filtered, narrow) for y in range(my) for _ in range(runs)]
+
+
+def wave_steps(recs, cus, kernel, form="any", S=None):
+    """Every (record, unit of it) -> (record, unit of it) one wave of the simulated deal takes directly one behind the other (S: a share given, not worked out)."""
+    K = KERNELS[kernel]; W = K["waves"]
+    live = [r for r in recs if r.sizes is not None]
+    where = [(k, lu) for k, r in enumerate(live) for lu in range(r.units)]
+    T = len(where); S = S or share(T, cus, K["per_cu"][per_cu_form(kernel, form)], W)
+    return [(where[u], where[u + W]) for u in range(T - W) if u // S == (u + W) // S]
+
+
+def adjacency_missing(recs, cus, denom=1):
+    """The entries of ADJACENT no wave of the deal meets, for k_render_ijg (denom 1) or k_render_ijg_scaled."""
+    kernel = "render" if denom == 1 else "render_scaled"
+    live = [r for r in recs if r.sizes is not None]
+    kinds = {r.pic: _kinds(r.pic, denom) for r in live}
+    met = set()
+    for (k, lu), (j, lv) in wave_steps(recs, cus, kernel):
+        a, b = kinds[live[k].pic][lu], kinds[live[j].pic][lv]
+        if a[0] != "grey" and b[0] == "grey":
+            met.add(ADJACENT[0])
+        if a[0] == "420" and b[0] == "444":
+            met.add(ADJACENT[1])
+        if a[0] == "422" and b[0] == "420":
+            met.add(ADJACENT[2])
+        if a[1] and b[2]:
+            met.add(ADJACENT[3])
+        if a[1] and b[3]:
+            met.add(ADJACENT[4])
+        if a[4] and 0 < b[5] <= 2:
+            met.add(ADJACENT[5])
+        if a[4] and b[5] == 3:
+            met.add(ADJACENT[6])
+    asked = ADJACENT[:5] + (ADJACENT[5:6] if denom == 1 else ADJACENT[5:] if render_filters(denom) else ())
+    return [name for name in asked if name not in met]
+
+
+def render_pictures(denom=1):
+    """(short candidates, long pictures, prelude).  `px(mode)` is the width in pixels of a full unit: widths are stated in it, so the lists have the same units at
+    every denominator.  One-unit pictures: a 4:2:2 one whose chroma plane is two samples wide, a grey one that fills its unit, and one whose chroma plane is
+    two (4:2:0, full size) or three (4:2:2, scaled) samples wide.  Long ones: two tall pictures one MCU wide, grey and 4:2:0; a 4:2:0 picture of two full runs
+    and a short one, sixteen MCU rows; a 4:2:2 picture of a full and a short run; a 4:4:4 picture of one full run.  The prelude puts a long picture of one
+    kind directly in front of short ones of another; in the body the tall 4:2:0 picture stands in front of the wide one."""
+    px = lambda mode: 64 * IC.HV[mode][0][0] if denom == 1 else 64 * denom
+    two = ("422", 4, 8) if denom == 1 else ("422", 4 * denom, 8)
+    three = ("420", 3, 13) if denom == 1 else ("422", 4 * denom + denom // 2, 8)
+    shorts = [two, ("grey", px("grey"), 5), three, ("420", 3, 17), ("444", px("444") + 8, 8), ("422", 2 * px("422") + 5, 8), ("grey", 13, 24), ("420", 16, 79), ("444", 20, 40)]
+    tall, wide, l422 = ("420", 16, 16 * 67), ("420", 2 * px("420") + px("420") // 4 + 5, 16 * 16 - 3), ("422", px("422") + px("422") // 8 + 2, 8 * 30)
+    longs = [("grey", 8, 8 * 101), tall, wide, l422, ("444", px("444"), 8 * 50)]
+    prelude = [wide, ("444", 20, 40), l422, ("420", 16, 79), l422, two, three, ("grey", 13, 24), tall, ("420", 16, 79)]
+    return shorts, longs, prelude
+
+
+def _render_build(kernel, form, cus, denom, sizes_of):
+    shorts, longs, prelude = render_pictures(denom)
+    recs = _build(kernel, form, cus, shorts, longs, sizes_of, per=3, prelude=prelude, also=lambda recs, cus: adjacency_missing(recs, cus, denom))
+    assert adjacency_missing(recs, cus, denom) == []
+    full = KERNELS[kernel]["unit"]
+    assert any(r.units >= 48 and r.sizes[:2] == [full, full] and render_grid(r.pic, denom)[5] >= 3 for r in recs), "a long picture wider than two full runs"
+    assert {r.pic[0] for r in recs if r.units >= 48} == set(IC.MODES) == {r.pic[0] for r in recs if r.units <= 5}, "all four modes among the long and the short pictures"
+    return recs
+
+
+def render_records(cus, form="any"):
+    return _render_build("render", "any", cus, 1, render_sizes)
+
+
+def render_scaled_records(cus, denom):
+    return _render_build("render_scaled", str(denom), cus, int(denom), lambda p: render_scaled_sizes(p, int(denom)))
+
+
+def deal_place(recs, cus, kernel, form, k, lu):
+    """Where the deal puts unit `lu` of live record k: for a failure message that can be read without another run."""
+    K = KERNELS[kernel]; W = K["waves"]
+    live = [r for r in recs if r.sizes is not None]
+    T = sum(r.units for r in live); S = share(T, cus, K["per_cu"][per_cu_form(kernel, form)], W)
+    u = sum(r.units for r in live[:k]) + lu; g = u // S
+    return "unit %d of the call = unit %d of record %d: share %d (units %d..%d, S = %d), wave %d, its turn %d" % (u, lu, k, g, g * S, min(T, g * S + S) - 1, S, (u - g * S) % W, (u - g * S) // W)
+
+
+BUILDERS = {("render", "any"): render_records, ("render_scaled", "2"): lambda cus: render_scaled_records(cus, 2), ("render_scaled", "4"): lambda cus: render_scaled_records(cus, 4),
+            ("render_scaled", "8"): lambda cus: render_scaled_records(cus, 8),
+            ("encode", "420"): lambda cus: encode_records(cus, "420"), ("encode", "422"): lambda cus: encode_records(cus, "422"),
             ("transform", "plain"): lambda cus: transform_records(cus, "plain"), ("transform", "turned"): lambda cus: transform_records(cus, "turned"),
             ("coefs", "direct"): lambda cus: coefs_records(cus, "direct"), ("coefs", "tiled"): lambda cus: coefs_records(cus, "tiled"),
             ("stats", "hist"): lambda cus: stats_records(cus, "hist"), ("stats", "plain"): lambda cus: stats_records(cus, "plain"),

@@ -33,7 +33,8 @@ def test_share_is_the_grid_rule_and_capis():
             for R in (1, 16, 127):
                 assert D.share(total, cus, K["per_cu"]["any"], K["waves"]) == capi.coef_hist_share(total, cus, R), (cus, total, R)
     # below W * F * cus units a share is W units and a wave takes one: the regime of every test but the new ones (the largest calls the suite made before)
-    for kernel, form, most in (("encode", "any", 100), ("transform", "any", 3600), ("coefs", "direct", 4500), ("coefs", "tiled", 4500), ("stats", "hist", 400), ("coef_hist", "any", 100)):
+    for kernel, form, most in (("encode", "any", 100), ("transform", "any", 3600), ("coefs", "direct", 4500), ("coefs", "tiled", 4500), ("stats", "hist", 400), ("coef_hist", "any", 100),
+                               ("render", "any", 1000), ("render_scaled", "any", 1000)):
         K = D.KERNELS[kernel]
         assert most <= K["waves"] * K["per_cu"][form] * 256 and D.share(most, 256, K["per_cu"][form], K["waves"]) == K["waves"], (kernel, form)
         assert D.share(K["waves"] * K["per_cu"][form] * 256 + 1, 256, K["per_cu"][form], K["waves"]) == K["waves"] + 1
@@ -161,6 +162,12 @@ def test_every_builder_meets_the_conditions_of_its_gpu_test(key):
         assert any(0 < k < len(live) - 1 and live[k - 1].units <= 5 * step and live[k + 1].units <= 5 * step for k in k_long), "a long record between short ones"
         if need.get("narrow"):
             assert any(min(r.sizes) < K["unit"] for r in live if r.units >= 3 * c.S) and any(max(r.sizes) == K["unit"] for r in live if r.units >= 3 * c.S)
+        if kernel in ("render", "render_scaled"):
+            denom = 1 if kernel == "render" else int(form)
+            assert D.adjacency_missing(recs, cus, denom) == [], cus
+            assert adjacency_by_the_transcription(recs, c, W, denom) >= set(D.ADJACENT[:5] + D.ADJACENT[5:{1: 6, 2: 7, 4: 7, 8: 5}[denom]]), cus
+            assert {r.pic[0] for r in live if r.units >= 3 * c.S} == set(D.IC.MODES) == {r.pic[0] for r in live if r.units <= 5}, "all four modes, long and short"
+            assert any(r.units >= 3 * c.S and D.render_grid(r.pic, denom)[5] >= 3 and r.sizes[:2] == [K["unit"]] * 2 for r in live), "a long picture wider than two full runs"
         refused = [k for k, r in enumerate(recs) if r.sizes is None]
         if kernel == "transform":
             assert refused and all(0 < k < len(recs) - 1 and (recs[k - 1].sizes and recs[k + 1].sizes) for k in refused), "refused entries sit among those that are OK"
@@ -169,8 +176,61 @@ def test_every_builder_meets_the_conditions_of_its_gpu_test(key):
             assert not refused
 
 
+def adjacency_by_the_transcription(recs, c, W, denom):
+    """The entries of D.ADJACENT met along the kernels' own loop (`transcription`), each stated here on the pictures' numbers: a second walk beside
+    D.adjacency_missing, which goes through D.wave_steps and D._kinds."""
+    live = [r for r in recs if r.sizes is not None]
+    walk, _most = transcription([r.units for r in live], c.S, W, False)
+    base = [0]
+    for r in live:
+        base.append(base[-1] + r.units)
+    steps = [((k, u - base[k]), (j, v - base[j])) for waves in walk for t in waves for (u, k), (v, j) in zip(t, t[1:])]
+    assert sorted(steps) == sorted(D.wave_steps(recs, 0, "render", "any", S=c.S))
+
+    def unit(k, lu):
+        mode, w, h = live[k].pic; H, V = D.IC.HV[mode][0]
+        rows = -(-h // (8 * V)); across = -(-w // (8 * H)); run = 8 if denom == 1 else 64 // (H * (8 // denom))
+        my = lu // -(-across // run)
+        if denom == 1:
+            cw = -(-w // 2) if H == 2 else None                   # the chroma plane's width where chroma is upsampled horizontally
+            filtered = H == 2 and cw > 2
+        else:
+            cw = -(-(w * (8 // denom)) // 16) if mode == "422" else None      # 4:2:2: nc = m samples per block
+            filtered = mode == "422" and denom in (2, 4) and cw > 2
+        return mode, my, rows, cw, filtered
+
+    met = set()
+    for a, b in steps:
+        (ma, ya, ra, _ca, fa), (mb, yb, rb, cb, _fb) = unit(*a), unit(*b)
+        interior = ma == "420" and ra >= 3 and 0 < ya < ra - 1
+        met |= {name for name, hit in zip(D.ADJACENT, (ma != "grey" and mb == "grey", ma == "420" and mb == "444", ma == "422" and mb == "420",
+                                                         interior and mb == "420" and rb >= 2 and yb == 0, interior and mb == "420" and rb >= 2 and yb == rb - 1,
+                                                         fa and cb is not None and cb <= 2, fa and cb == 3)) if hit}
+    return met
+
+
+def test_render_sizes_are_the_unit_counts_of_the_plans():
+    """js_ren_units / js_rs_units restated: mcu_ymax * ceil(mcu_xmax / run), run = JS_REN_RUN or 64 / (H m).  The GPU tests tie the counts to the batch's geometry."""
+    for denom in (1, 2, 4, 8):
+        shorts, longs, prelude = D.render_pictures(denom)
+        assert set(prelude) <= set(shorts) | set(longs)
+        for pic in shorts + longs + [(mode, w, h) for mode in D.IC.MODES for w, h in D.IC.SIZES + [(449, 33), (1025, 17)]]:
+            mode, w, h = pic; H, V = D.IC.HV[mode][0]; m = 8 // denom
+            mcu_xmax, mcu_ymax = (w + 8 * H - 1) // (8 * H), (h + 8 * V - 1) // (8 * V)
+            run = 8 if denom == 1 else 64 // (H * m)
+            sizes = D.render_sizes(pic) if denom == 1 else D.render_scaled_sizes(pic, denom)
+            assert len(sizes) == mcu_ymax * ((mcu_xmax + run - 1) // run), (pic, denom)
+            assert sum(sizes) == mcu_xmax * mcu_ymax * (1 if denom == 1 else H * m) and max(sizes) <= D.KERNELS["render" if denom == 1 else "render_scaled"]["unit"], (pic, denom)
+            assert all(sizes[i] == sizes[i % (len(sizes) // mcu_ymax)] for i in range(len(sizes))), "every MCU row has the same runs"
+    # the pictures the adjacency conditions name: chroma two samples wide at full size (3 and 4 pixels), two and three at 1/2 (8 and 9 pixels of 4:2:2)
+    assert [D.render_chroma(p) for p in (("422", 4, 8), ("420", 3, 13), ("422", 5, 8))] == [(2, False), (2, False), (3, True)]
+    assert [D.render_chroma(("422", w, 8), 2) for w in (8, 9)] == [(2, False), (3, True)] and D.render_chroma(("422", 16, 8), 4) == (2, False)
+    assert D.render_chroma(("422", 200, 8), 8)[1] is False and D.render_chroma(("420", 200, 8), 2)[1] is False and not D.render_filters(8)
+
+
 def test_the_forms_of_the_gpu_tests_are_all_here():
-    assert sorted(D.BUILDERS) == [("coef_hist", "any"), ("coefs", "direct"), ("coefs", "tiled"), ("encode", "420"), ("encode", "422"), ("stats", "hist"), ("stats", "plain"),
+    assert sorted(D.BUILDERS) == [("coef_hist", "any"), ("coefs", "direct"), ("coefs", "tiled"), ("encode", "420"), ("encode", "422"), ("render", "any"),
+                                  ("render_scaled", "2"), ("render_scaled", "4"), ("render_scaled", "8"), ("stats", "hist"), ("stats", "plain"),
                                   ("transform", "plain"), ("transform", "turned")]
     import transform_model as TM
     assert TM.OPS[D.TRANSFORM_FORMS["plain"]["op"]] not in TM.TRANSPOSING and TM.OPS[D.TRANSFORM_FORMS["turned"]["op"]] in TM.TRANSPOSING

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import coef_model as CM
+import deal_cases as D
 import fuzz_util as F
 import ijg_cases as IC
 import ijg_model as M
@@ -129,9 +130,10 @@ class Arena:
     """One device allocation of 0xA5 bytes holding every destination of a call, and the bytes the model says it must hold afterwards."""
 
     def __init__(self, torch, sizes, lead=0):
+        """lead: bytes past a 16-byte boundary every destination starts at, or one number per destination."""
         self.offs, pos = [], GUARD
-        for nb in sizes:
-            pos = (pos + 15) // 16 * 16 + lead
+        for k, nb in enumerate(sizes):
+            pos = (pos + 15) // 16 * 16 + (lead[k] if isinstance(lead, (list, tuple)) else lead)
             self.offs.append(pos)
             pos += nb + GUARD
         self.buf = torch.full((pos,), 0xA5, dtype=torch.uint8, device="cuda")
@@ -265,6 +267,105 @@ def test_a_shuffled_subset_and_an_image_listed_twice(J, torch, mixed):
     order = [int(i) for i in np.random.default_rng(4).permutation(n)[:9]] + [11, 2, 11]
     render_and_check(J, torch, m["b"], m["models"], "HWC", "uint8", order, what="shuffled")
     render_and_check(J, torch, m["b"], m["models"], "CHW", "float32", order, scale=SCALE, bias=BIAS, what="shuffled")
+
+
+# ------------------------------------------------------------------------------------------------ the deal: a wave walks several units and records
+def deal_files(harness, distinct, progressive):
+    """[(file, Pillow's own)] -- one file per distinct picture of a deal list, in its order (a batch holds one kind of file, so there are two lists).
+    Baseline: Pillow's files of seeded noise at varying quality, and from the generator, with restart intervals, the long 4:2:2 picture and a grey one of
+    three MCU rows.  Progressive: Pillow's, every one."""
+    out = []
+    for k, pic in enumerate(distinct):
+        mode, w, h = pic
+        if not progressive and pic == ("grey", 13, 24):
+            out.append((harness.synth_jpeg(width=w, height=h, gray=1, restart_interval=1, seed=60 + k), False))
+        elif not progressive and mode == "422" and h >= 8 * 30:
+            out.append((harness.synth_jpeg(width=w, height=h, hs=2, vs=1, quality=60, restart_interval=5, seed=60 + k), False))
+        else:
+            # (Pillow gives libjpeg one buffer of width x height bytes for a progressive file: noise in colour passes it above quality 60)
+            out.append((IC.pillow_file(IC.noise(w, h, 300 + k), mode, (10, 40, 25, 60)[k % 4] if progressive else IC.QUALITIES[k % 4], progressive=bool(progressive)), True))
+    assert progressive or sum(not own for _f, own in out) == 2
+    return out
+
+
+def deal_where(ar, recs, image, meta, cus, denom):
+    """None when the arena holds what the model says, or the first wrong byte as record, picture, pixel, MCU, unit -- and where the deal put that unit."""
+    got = ar.buf.cpu().numpy()
+    if np.array_equal(got, ar.expect):
+        return None
+    bad = int(np.flatnonzero(got != ar.expect)[0])
+    k = max([i for i, o in enumerate(ar.offs) if o <= bad], default=-1)
+    where = "outside every destination (arena offset %d, destination %d starts at %d)" % (bad, k, ar.offs[k] if k >= 0 else 0)
+    if k >= 0 and bad - ar.offs[k] < ar.sizes[k]:
+        layout, elem, rp, pp, w, h = meta[k]; o = bad - ar.offs[k]; pic = recs[k].pic
+        if layout == "HWC":
+            y, x, ch = o // rp, (o % rp) // (3 * elem), ((o % rp) // elem) % 3
+        else:
+            ch, y, x = o // pp, (o % pp) // rp, ((o % pp) % rp) // elem
+        gap = " -- in a pitch gap, the unit is that of the nearest pixel" if (x >= w or y >= h) else ""
+        x, y = min(x, w - 1), min(y, h - 1)
+        H, V, _mx, _my, run, runs = D.render_grid(pic, denom); m = 8 // denom
+        mcu_x, my = x // (H * m), y // (V * m); lu = my * runs + mcu_x // run
+        where = "record %d, picture %s (image %d) at 1/%d, channel %d, pixel (x %d, y %d)%s of MCU (%d, %d): unit lu = %d (my %d, m0 %d), destination byte %d; %s" % (
+            k, pic, image[pic], denom, ch, x, y, gap, mcu_x, my, lu, my, mcu_x // run * run, o,
+            D.deal_place(recs, cus, "render" if denom == 1 else "render_scaled", "any", k, lu))
+    return "first wrong byte in %s: got 0x%02x, want 0x%02x; %d bytes differ" % (where, got[bad], ar.expect[bad], int((got != ar.expect).sum()))
+
+
+def deal_render_and_check(J, torch, recs, image, model_of, call, layout, dtype, cus, denom, what, scale=None, bias=None):
+    """One raw call (call(spec, images, dsts)) with one destination per record of a deal list, then the whole arena against the models.  Records of the same
+    picture are not interchangeable: every third destination is dense (pitches passed as 0), the others have row and plane pitches and all have leads that
+    vary with the record index (float32: multiples of 4)."""
+    elem = 4 if dtype == "float32" else 1
+    formed = {p: form(model_of(i), layout, dtype, False, scale, bias) for p, i in image.items()}
+    geo, lead, meta = [], [], []
+    for k, r in enumerate(recs):
+        h, w = model_of(image[r.pic]).shape[:2]
+        dense = k % 3 == 0
+        rp = w * elem * (3 if layout == "HWC" else 1) + (0 if dense else (1 + k % 5) * elem)
+        pp = h * rp + (0 if dense else (k % 4) * elem)
+        geo.append((rp, pp, h * rp if layout == "HWC" else 3 * pp, dense)); lead.append(k % 16 if elem == 1 else 4 * (k % 4))
+        meta.append((layout, elem, rp, pp, w, h))
+    ar = Arena(torch, [g[2] for g in geo], lead)
+    for k, r in enumerate(recs):
+        ar.place(k, formed[r.pic], layout, geo[k][0], geo[k][1])
+    dsts = [(ar.ptr(k), 0 if dense else rp, 0 if dense or layout == "HWC" else pp) for k, (rp, pp, _nb, dense) in enumerate(geo)]
+    torch.cuda.synchronize()                                      # (the fill above ran on torch's stream, the render runs on the batch's)
+    assert call(make_spec(J, layout, dtype, False, scale, bias), [image[r.pic] for r in recs], dsts) == 0, J.last_error()
+    torch.cuda.synchronize()
+    wrong = deal_where(ar, recs, image, meta, cus, denom)
+    assert wrong is None, "%s %s %s: %s" % (what, layout, dtype, wrong)
+
+
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(J, torch, harness, capsys):
+    """Every test above stays far below RN_WAVES * 6 * compute units units, where a workgroup's share is four units and a wave takes one.  Here the call is
+    sized from the device (tests/deal_cases.py; tests/test_deal_cases.py proves the lists on the CPU): a share of twelve units, every wave takes three
+    one after the other through the same LDS -- luma rectangle, chroma planes, halo columns and rows, transpose tile --, reloads its record, passes over
+    one-unit records, and takes a grey unit behind a colour one, 4:4:4 behind 4:2:0, 4:2:0 behind 4:2:2, a chroma plane two samples wide behind a
+    filtered unit, a first and a last MCU row behind an interior unit of 4:2:0 (D.ADJACENT).  Fourteen distinct pictures, each once in the batch and
+    listed once per record with a destination of its own shape; a baseline batch rendered HWC uint8, a progressive one CHW float32.  Everything
+    against the model of the batch's own arena, and that against Pillow."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    recs = D.render_records(cus)
+    c = D.census_of("render", "any", recs, cus)
+    with capsys.disabled():
+        print("\nk_render_ijg, %d compute units: %s; %d records of %d pictures" % (cus, D.summary(c), len(recs), len({r.pic for r in recs})))
+    assert D.missing(c, D.KERNELS["render"]["waves"], **D.conditions("render", "any")) == [] and D.adjacency_missing(recs, cus) == [], D.summary(c)
+    distinct = sorted({r.pic for r in recs}); image = {p: i for i, p in enumerate(distinct)}
+    for progressive, (layout, dtype), sb in ((0, ("HWC", "uint8"), (None, None)), (1, ("CHW", "float32"), (SCALE, BIAS))):
+        files = deal_files(harness, distinct, progressive)
+        b = decoded_batch(J, [f for f, _own in files])
+        try:
+            models = models_of(J, torch, b)
+            for i, (f, own) in enumerate(files):
+                assert not own or np.array_equal(models[i], IC.pillow_pixels(f)), distinct[i]
+            for r in recs:                                            # the units the census counted are the units of the call
+                inf = b.info(image[r.pic])
+                assert r.units == inf["mcu_ymax"] * -(-inf["mcu_xmax"] // D.KERNELS["render"]["unit"]) and sum(r.sizes) == inf["mcu_xmax"] * inf["mcu_ymax"], r.pic
+            deal_render_and_check(J, torch, recs, image, lambda i: models[i], lambda spec, images, dsts: raw_ijg(J, b, spec, images, dsts), layout, dtype, cus, 1,
+                                  "deal, %s batch" % ("progressive" if progressive else "baseline"), scale=sb[0], bias=sb[1])
+        finally:
+            b.close()
 
 
 # ------------------------------------------------------------------------------------------------ source kinds

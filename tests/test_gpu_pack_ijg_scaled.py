@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import deal_cases as D
 import fuzz_util as F
 import ijg_cases as IC
 import ijg_model as M
@@ -233,6 +234,40 @@ def test_reduce_1_is_the_full_size_render_and_the_other_paths_give_what_they_gav
     b.to_torch(layout="CHW", pixels="libjpeg", reduce=8)
     after = b.to_torch(layout="HWC")
     assert all(np.array_equal(x, y.cpu().numpy()) for x, y in zip(before, after))
+
+
+# ------------------------------------------------------------------------------------------------ the deal: a wave walks several units and records
+@pytest.mark.parametrize("s", S.SCALES)
+def test_calls_of_so_many_units_that_a_wave_walks_several_units_and_records(J, torch, harness, capsys, s):
+    """Every test above stays far below RS_WAVES * 6 * compute units units, where a workgroup's share is four units and a wave takes one.  Here the call is
+    sized from the device (tests/deal_cases.py; tests/test_deal_cases.py proves the lists on the CPU): a share of twelve units, every wave takes three
+    one after the other through the same LDS -- three planes, the 4:2:2 halo columns, load tile and workspace --, reloads its record, passes over one-unit
+    records, and sees H, V, ncomp, bpm, run, ny and nc change from one unit to the next: grey behind colour, 4:4:4 behind 4:2:0, 4:2:0 behind 4:2:2 and,
+    where 4:2:2 is filtered (1/2, 1/4), chroma planes two and three samples wide behind a filtered unit (D.ADJACENT).  Fourteen distinct pictures, their
+    widths stated in units, each once in the batch and listed once per record with a destination of its own shape; a baseline batch rendered HWC uint8
+    and, at 1/2, a progressive one CHW uint8.  Everything against the model of the batch's own arena, and that against Pillow's reduced decode."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    K = D.KERNELS["render_scaled"]; m = 8 // s
+    recs = D.render_scaled_records(cus, s)
+    c = D.census_of("render_scaled", str(s), recs, cus)
+    with capsys.disabled():
+        print("\nk_render_ijg_scaled 1/%d, %d compute units: %s; %d records of %d pictures" % (s, cus, D.summary(c), len(recs), len({r.pic for r in recs})))
+    assert D.missing(c, K["waves"], **D.conditions("render_scaled", str(s))) == [] and D.adjacency_missing(recs, cus, s) == [], D.summary(c)
+    distinct = sorted({r.pic for r in recs}); image = {p: i for i, p in enumerate(distinct)}
+    for progressive, layout in ((0, "HWC"), (1, "CHW"))[:2 if s == 2 else 1]:
+        files = T.deal_files(harness, distinct, progressive)
+        b = T.decoded_batch(J, [f for f, _own in files])
+        try:
+            models = models_of(J, torch, b, (s,))
+            for i, (f, own) in enumerate(files):
+                assert not own or np.array_equal(models[i, s], S.pillow_reduced(f, s)), (distinct[i], s)
+            for r in recs:                                            # the units the census counted are the units of the call
+                inf = b.info(image[r.pic]); H = inf["mcu_w"] // 8; run = K["unit"] // (H * m)
+                assert r.units == inf["mcu_ymax"] * -(-inf["mcu_xmax"] // run) and sum(r.sizes) == inf["mcu_xmax"] * inf["mcu_ymax"] * H * m, (r.pic, s)
+            T.deal_render_and_check(J, torch, recs, image, lambda i: models[i, s], lambda spec, images, dsts: raw_scaled(J, b, spec, s, images, dsts), layout, "uint8", cus, s,
+                                    "deal at 1/%d, %s batch" % (s, "progressive" if progressive else "baseline"))
+        finally:
+            b.close()
 
 
 # ------------------------------------------------------------------------------------------------ source kinds
